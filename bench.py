@@ -8,7 +8,7 @@ per GPU).  Synthetic COCO-shaped data generated on the device, random-init weigh
 assignment, forward, focal + smooth-L1, backward, bucketed RCCL all-reduce, clip and
 Keras-Adam update.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--conv-table PATH|tune] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 With ``--gpus N > 1`` and no launcher environment (``WORLD_SIZE`` / ``OMPI_COMM_WORLD_SIZE``),
@@ -73,7 +73,45 @@ def parse(argv=None):
                    help="re-run this benchmark as a child under rocprofv3: 'stats' = kernel trace + per-kernel "
                         "statistics (summarised by family), 'pmc' = MFMA / LDS / wait counters (kernel trace only)")
     p.add_argument("--profile-dir", default="gpurun_out/profile")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy "
+                        "(float32): the three losses train_on_batch returns, and fixed seeded samples of the "
+                        "gradients, weights and Adam first moments the step left behind")
+    p.add_argument("--conv-table", default=None, metavar="PATH",
+                   help="per-shape conv algorithm table the run starts from (sets MXR_CONV_TABLE).  Default: "
+                        "MXR_CONV_TABLE, else the committed tuning/conv_table.json, so that every run executes the "
+                        "same kernels and computes the same numbers; 'tune' races every shape on this GPU at "
+                        "first sight instead (near-ties then flip from run to run), as does MXR_SAVE_CONV_TABLE")
+    p.add_argument("--full", action="store_true",
+                   help="also run whatever the benchmark measures or checks beyond its headline figure; today a "
+                        "plain run does nothing of that kind, so the option adds nothing yet")
     return p.parse_args(argv)
+
+
+DUMP_SAMPLE = 4 * 1024 * 1024     # elements kept of each flat buffer: 3 x 16 MiB of float32, under the 64 MB cap
+DUMP_SEED = 20240229
+
+
+def dump_outputs(out_dir: str, logs, trainer) -> None:
+    """Write the last timed step's results as ``<out_dir>/<name>.npy`` (float32).  The flat gradient, weight and
+    Adam buffers of the flagship model are ~145 MB each, so each is sampled at the same seeded positions (drawn on
+    the CPU: identical for every build and device); a buffer no larger than the sample is written whole."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in (logs or {}).items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.asarray([float(v)], dtype=np.float32))
+    opt = trainer.optimizer
+    flats = {"grad": opt.flat.grad, "weights": opt.flat.data, "adam_m": opt.optimizer.m}
+    total = int(opt.flat.data.numel())
+    idx = None
+    if total > DUMP_SAMPLE:
+        g = torch.Generator(device="cpu")
+        g.manual_seed(DUMP_SEED)
+        idx = torch.randint(total, (DUMP_SAMPLE,), generator=g)
+    for k, t in flats.items():
+        t = t.detach().reshape(-1)
+        t = t if idx is None else t[idx.to(t.device)]
+        np.save(os.path.join(out_dir, k + ".npy"), t.to(torch.float32).cpu().numpy())
 
 
 PMC = ["SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_MFMA SQ_LDS_BANK_CONFLICT SQ_BUSY_CYCLES",
@@ -150,6 +188,26 @@ def check_rccl(info, world: int):
     return None
 
 
+DEFAULT_CONV_TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuning", "conv_table.json")
+
+
+def pin_conv_table(args) -> None:
+    """Choose the conv table this run (and the ranks it starts) begins with.  The tuner's first-sight races are
+    timing decisions: near-ties flip from run to run, and kernels that accumulate in another order round
+    differently, so two tuned runs of one build need not agree.  The benchmark therefore starts from the committed
+    table of the flagship configuration (every key of that run: nothing is raced); shapes the table lacks are
+    still raced.  ``--conv-table tune``, or asking for this run's table to be saved (MXR_SAVE_CONV_TABLE), tunes
+    from scratch as before."""
+    table = args.conv_table
+    if table is None:
+        table = os.environ.get("MXR_CONV_TABLE") or ("tune" if os.environ.get("MXR_SAVE_CONV_TABLE") else
+                                                      DEFAULT_CONV_TABLE)
+    if table in ("tune", ""):
+        os.environ.pop("MXR_CONV_TABLE", None)
+    else:
+        os.environ["MXR_CONV_TABLE"] = os.path.abspath(table)
+
+
 def spawn(args, argv) -> int:
     """Start ``--gpus`` ranks of this benchmark as child processes (this process never touches the
     GPU) and return the first failing exit code."""
@@ -164,6 +222,7 @@ def main(argv=None):
         return profile(args, argv)
     if args.comm:
         os.environ["MXR_COMM"] = args.comm
+    pin_conv_table(args)      # before the package import below: the tuner reads MXR_CONV_TABLE when it is created
     env_world = _launcher_world()
     if env_world is None and args.gpus > 1:
         return spawn(args, argv)
@@ -276,6 +335,8 @@ def main(argv=None):
         import torch.distributed as dist
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, logs, trainer)
     consistent, diverged = None, []
     if world > 1 or trainer.optimizer.native is not None:
         # after the timed region: the replicas must still hold bit-identical weights and Adam slots
@@ -335,6 +396,9 @@ def main(argv=None):
     try:
         from batchai_retinanet_horovod_coco_amd.ops.conv_tuner import TUNER
         res["config"]["conv_algos"] = TUNER.summary()
+        # the table the run started from (None: tuned from scratch) and how many shapes it still had to race
+        res["config"]["conv_table"] = os.environ.get("MXR_CONV_TABLE")
+        res["config"]["conv_raced"] = len(TUNER.timings)
         from batchai_retinanet_horovod_coco_amd.ops import conv_launch as _cl
         # forms adopted over a near-tie race winner (ConvTuner.prefer) and launches of the fused focal final
         res["config"]["preferred_forms"] = dict(TUNER.preferred)
