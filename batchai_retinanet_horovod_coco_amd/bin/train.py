@@ -9,7 +9,7 @@ Same subcommands, flags, defaults and argument checks as ``/root/reference/train
 ``--image-max-side``), plus a ``synthetic`` dataset and MI355X options (``--dtype``, ``--clip-mode``,
 ``--bucket-mb``, ``--allreduce-dtype``, ``--workers``, ``--shard-data``, ``--checkpoint-format``,
 ``--lr``, ``--clipnorm``, ``--seed``, ``--log-every``, ``--no-metric-average``, ``--log-all-ranks``,
-``--metrics-jsonl``, ``--stop-on-nan``).
+``--metrics-jsonl``, ``--stop-on-nan``, ``--graph``, ``--graph-shapes``).
 
 Orchestration follows ``main()`` (``train.py:383-450``): init the data-parallel runtime
 (``hvd.init()``), backbone object, generators, model (snapshot or weights), summary, callbacks
@@ -48,6 +48,11 @@ def check_args(parsed_args):
     if parsed_args.multi_gpu > 1 and not parsed_args.multi_gpu_force:
         raise ValueError("Multi-GPU support is experimental, use at own risk! Run with --multi-gpu-force if you wish "
                          "to continue.")
+    if getattr(parsed_args, "graph", False) and parsed_args.dtype == "fp8":
+        raise SystemExit("--graph cannot be combined with --dtype fp8: the fp8 delayed-scaling state advances on "
+                         "the host every step, which a replayed step would skip")
+    if getattr(parsed_args, "graph_shapes", 1) < 1:
+        raise SystemExit("--graph-shapes must be at least 1")
     if "resnet" not in parsed_args.backbone:
         warnings.warn("Using experimental backbone {}. Only resnet50 has been properly tested.".format(
             parsed_args.backbone))
@@ -160,6 +165,12 @@ def build_parser() -> argparse.ArgumentParser:
                         help="Pad each batch's H and W up to a multiple of this (shape classes for the conv tuner; "
                              "the extra anchors lie outside every image and are ignored).  Default: 32 (the C5 "
                              "stride) on a GPU, 0 (batch max only, the reference) on the CPU; 128 = the P7 stride.")
+    parser.add_argument("--graph", action="store_true",
+                        help="Train through HIP-graph-captured steps, one per batch shape class (bit-identical to "
+                             "the eager step; removes the host's per-kernel launch cost at small batches).  A class "
+                             "runs eagerly twice, then is captured and replayed.  GPU, bf16 / fp32 compute.")
+    parser.add_argument("--graph-shapes", type=int, default=8, metavar="N",
+                        help="With --graph: capture at most N shape classes; further classes stay eager.")
     return parser
 
 
@@ -170,13 +181,19 @@ def parse_args(args):
 # ------------------------------------------------------------------------------ generators
 def create_generators(args, shard=None):
     from ..data.transform import random_transform_generator
+    prng = None
+    if args.seed is not None:
+        # --seed covers the augmentation draws too (unseeded, as in the reference, without it): two runs with the
+        # same seed see the same batches
+        import numpy as np
+        prng = np.random.RandomState(args.seed)
     if args.random_transform:
         transform_generator = random_transform_generator(
-            min_rotation=-0.1, max_rotation=0.1, min_translation=(-0.1, -0.1), max_translation=(0.1, 0.1),
+            prng=prng, min_rotation=-0.1, max_rotation=0.1, min_translation=(-0.1, -0.1), max_translation=(0.1, 0.1),
             min_shear=-0.1, max_shear=0.1, min_scaling=(0.9, 0.9), max_scaling=(1.1, 1.1),
             flip_x_chance=0.5, flip_y_chance=0.5)
     else:
-        transform_generator = random_transform_generator(flip_x_chance=0.5)
+        transform_generator = random_transform_generator(prng=prng, flip_x_chance=0.5)
     common = dict(batch_size=args.batch_size, image_min_side=args.image_min_side, image_max_side=args.image_max_side,
                   pad_multiple=getattr(args, "pad_multiple", None) or 0)
     train_kw = dict(common, transform_generator=transform_generator, seed=args.seed, shard=shard)
@@ -396,11 +413,21 @@ def main(args=None):
         from ..ops.anchors import make_shapes_callback
         trainer.shapes_callback = make_shapes_callback(model)
 
+    if args.graph:
+        if dev.type != "cuda":
+            if rank == 0:
+                print("--graph: HIP graphs need a GPU; training eagerly on {}".format(dev.type), flush=True)
+        else:
+            trainer.enable_graphs(max_shapes=args.graph_shapes)
+
     if args.bench is not None:
         res = _bench(trainer, train_generator, args.bench[0], args.bench[1], dev, world=runtime.size(),
                      workers=args.workers, loader=args.loader, pad_multiple=args.pad_multiple)
         if rank == 0:
             print(json.dumps(res), flush=True)
+            if os.environ.get("MXR_SAVE_CONV_TABLE"):       # this run's tuned conv table, as bench.py saves it
+                from ..ops.conv_tuner import TUNER
+                TUNER.save(os.environ["MXR_SAVE_CONV_TABLE"])
         runtime.shutdown()
         return 0
 
@@ -412,6 +439,8 @@ def main(args=None):
                             verbose=verbose, callbacks=callbacks, initial_epoch=initial_epoch,
                             workers=args.workers, max_queue_size=args.max_queue_size, log_every=args.log_every,
                             loader=args.loader)
+    if trainer.step_graphs is not None and rank == 0:
+        print("step graphs: " + json.dumps(trainer.step_graphs.stats()), flush=True)
     runtime.shutdown()
     return history
 
@@ -449,8 +478,12 @@ def _bench(trainer, generator, warmup: int, steps: int, dev, world: int, workers
         return trainer.train_on_batch(b["images"], b["gt"], b["gt_count"], b["image_hw"])
 
     try:
-        for _ in range(max(1, warmup)):
+        from ..ops.conv_tuner import TUNER
+        graphs = getattr(trainer, "step_graphs", None)
+        for i in range(max(1, warmup)):
             one()
+            if graphs is not None and _rt.distributed() and TUNER.sync_due(i):
+                TUNER.sync_all()    # multi-rank step graphs are captured after the first table merge
         if dev.type == "cuda":
             torch.cuda.synchronize()
         _rt.barrier()
@@ -459,7 +492,6 @@ def _bench(trainer, generator, warmup: int, steps: int, dev, world: int, workers
         # steps that met a new batch shape tune its conv keys inside the timed region (the real-JPEG fixture has
         # two orientations; the first sight of the second one can land after the warm-up): per-step GPU time
         # from events, and the steady rate over the steps that tuned nothing
-        from ..ops.conv_tuner import TUNER
         marks = []
         t0 = time.perf_counter()
         b0 = len(TUNER.borrowed)
@@ -523,7 +555,8 @@ def _bench(trainer, generator, warmup: int, steps: int, dev, world: int, workers
             "warmup": warmup, "ms_per_step": round(1000 * el / max(steps, 1), 3), "n_ranks": world,
             "loss": float(logs["loss"]), "loader": type(enq).__name__, "workers": workers,
             "loader_wait_ms": round(1000 * wait[0] / max(steps, 1), 3),
-            "loader_wait_frac": round(wait[0] / max(t1 - t0, 1e-9), 4)}
+            "loader_wait_frac": round(wait[0] / max(t1 - t0, 1e-9), 4),
+            "hip_graph": graphs.stats() if graphs is not None else False}
 
 
 if __name__ == "__main__":

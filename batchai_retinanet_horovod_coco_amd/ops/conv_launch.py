@@ -327,11 +327,13 @@ class FocalRequest:
     (``RetinaNet.forward`` hands the request to the final layer through its pad sink); when the layer's tuned
     kernel has the form, its forward writes no logits -- ``loss`` and the padded gradient rows come out of the
     epilogue -- else ``loss`` stays None and the loss kernel runs as before.  One object per Trainer: its
-    zero-padded gradient buffer persists across steps (columns past A * C are never written)."""
+    zero-padded gradient buffers persist across steps (columns past A * C are never written), one per shape a
+    captured step graph holds plus a floating one (``native.ShapeSlots``)."""
 
     def __init__(self, alpha: float = 0.25, gamma: float = 2.0):
         self.alpha, self.gamma = alpha, gamma
-        self._buf = None
+        self._buf = _n.ShapeSlots()
+        self._qbuf = _n.ShapeSlots()
         self.set(None, None, None, 0)
 
     def set(self, state, label, npos, A: int) -> None:
@@ -339,18 +341,13 @@ class FocalRequest:
         self.loss = None
 
     def dpad(self, n: int, p: int, ld: int, device) -> torch.Tensor:
-        key = (n, p, ld, str(device))
-        if self._buf is None or self._buf[0] != key:
-            self._buf = (key, torch.zeros((n, p, ld), dtype=torch.bfloat16, device=device))
-        return self._buf[1]
+        return self._buf.get((n, p, ld, str(device)),
+                             lambda: torch.zeros((n, p, ld), dtype=torch.bfloat16, device=device))
 
     def dpad_q(self, n: int, p: int, ld: int, device) -> torch.Tensor:
         """The zero-padded e5m2 gradient rows of the fp8 FOCAL form (columns past A * C are never written)."""
-        key = (n, p, ld, str(device))
-        b = getattr(self, "_qbuf", None)
-        if b is None or b[0] != key:
-            self._qbuf = b = (key, torch.zeros((n, p, ld), dtype=torch.uint8, device=device))
-        return b[1]
+        return self._qbuf.get((n, p, ld, str(device)),
+                              lambda: torch.zeros((n, p, ld), dtype=torch.uint8, device=device))
 
 
 # the fused focal form on or off (a switch for the tests' same-process comparisons, not an environment knob)

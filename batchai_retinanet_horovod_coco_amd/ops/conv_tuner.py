@@ -58,6 +58,10 @@ class ConvTuner:
         self._gen = 0       # bumped by every table / borrowed write (prefer and sync included): the memo's clock
         self.calls: Dict[str, int] = {}
         self.preferred: Dict[str, str] = {}     # key -> the raced winner a prefer() call replaced
+        # keys that met a HIP-graph capture untuned (the first candidate ran where an eager call would have raced
+        # or borrowed): a step-graph cache throws such a capture away (train.step_graphs)
+        self.capture_misses: list = []
+        self.syncs = 0          # sync_all() merges done across ranks (multi-rank step graphs wait for the first)
         # timed work per candidate: enough repetitions to fill ~budget ms (2 reps of a 50 us kernel
         # are within launch noise of each other)
         self.budget_ms = float(os.environ.get("MXR_CONV_TUNE_MS", "2.0"))
@@ -259,6 +263,8 @@ class ConvTuner:
         if name in cands:
             return cands[name]()
         if len(cands) == 1 or not self._tuning_allowed():
+            if len(cands) > 1 and _env(b"MXR_CONV_TUNE", "1") == "1":
+                self.capture_misses.append(key)       # tuning is on, so the stream is capturing
             return next(iter(cands.values()))()
         name = self._borrow(key, set(cands))
         if name is not None:
@@ -356,6 +362,7 @@ class ConvTuner:
         with self.lock:
             mine = dict(self.table)
         tables = collectives.allgather_object(mine)
+        self.syncs += 1
         merged: Dict[str, str] = {}
         for t in reversed(tables):          # rank 0 written last: its choice wins
             merged.update(t)

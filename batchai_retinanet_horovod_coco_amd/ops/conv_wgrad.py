@@ -42,6 +42,33 @@ _WGRAD_P8 = {20: 0, 21: 1, 22: 2, 23: 3, 24: 4, 25: 5}
 
 _WGRAD_PIPE_OCC = {10: 2, 11: 3, 12: 4, 13: 2, 14: 2, 15: 2}
 
+# slab-free ("direct") forms of conv_wgrad_pipe.hip: variant -> ((TK, TC), kernel variant, the slab variant of the
+# same tile).  One split over the whole pixel range, the epilogue writes / accumulates the gradient itself: no
+# workspace, no reduce launch.
+_WGRAD_DIRECT = {30: ((128, 128), 0, 13), 31: ((64, 64), 1, 12)}
+# candidates only where the tile count alone gives a useful grid and the pixel range one block walks is short.
+# Sweep (profiles/r7_wgrad_direct_sweep.txt, R50-FPN layers at 1 / 2 / 4 images): the direct form wins up to 1,092
+# pixels (1.05-1.56x at >= 144 tiles) and loses from 2,100 pixels on (<= 0.82x) and at 128 tiles / 1,050 pixels
+# (0.70x).  The bounds only prune hopeless races; the tuner decides.
+DIRECT_MIN_TILES = 128       # 64 x 64 tiles of the output
+DIRECT_MAX_PIXELS = 1536
+
+
+def direct_covers(g: ConvGeom) -> bool:
+    """Single-geometry keys the slab-free weight gradient is raced for (the small-M layers of a one- to four-image
+    step: stage 4 / 5, FPN P5-P7)."""
+    if g.nlev != 1 or g.cin % 8 or g.ostride != 1:
+        return False
+    K = g.kh * g.kw * g.cin
+    tiles = -(-K // 64) * -(-g.cout // 64)
+    return tiles >= DIRECT_MIN_TILES and g.M <= DIRECT_MAX_PIXELS
+
+
+def _wgrad_variants(g: ConvGeom):
+    vs = list(_WGRAD_TILE) + list(_WGRAD_PIPE_TILE) + list(_WGRAD_P8)
+    return vs + list(_WGRAD_DIRECT) if direct_covers(g) else vs
+
+
 def _splits_pipe(g: ConvGeom, tk: int, tc: int, occ: int = 1) -> int:
     """Pixel splits so the grid is ~192 x ``occ`` blocks (``occ`` blocks on three quarters of the 256 CUs),
     each split >= 8 sub-stages of 32 rows.  The weight gradients run on the side stream next to the data-gradient chain:
@@ -59,8 +86,9 @@ def _splits_pipe(g: ConvGeom, tk: int, tc: int, occ: int = 1) -> int:
 
 def conv_wgrad(x, dy, g: ConvGeom, scale: Optional[torch.Tensor], out: Optional[torch.Tensor] = None,
                accumulate: bool = False, variant: Optional[int] = None, bias_out: Optional[torch.Tensor] = None,
-               bias_accumulate: bool = False) -> torch.Tensor:
+               bias_accumulate: bool = False, splits: Optional[int] = None) -> torch.Tensor:
     """fp32 dW (OHWI) = scale[co] * sum_m dY (x) im2col(X); dY may have cout % 8 != 0 (padded).
+    ``splits``: the pixel-split count of the split-K forms (default: the per-kernel heuristic).
     ``bias_out`` (phase-pipelined variants, see :data:`_WGRAD_P8`, cout % 4 == 0): the unscaled bias
     gradient sum_m dY[m, :cout] is computed by the same kernel from the dY tiles it stages anyway."""
     cout = g.cout
@@ -79,8 +107,17 @@ def conv_wgrad(x, dy, g: ConvGeom, scale: Optional[torch.Tensor], out: Optional[
                                  or bias_out.dtype != torch.float32 or not bias_out.is_contiguous()):
         raise RuntimeError("conv_wgrad: the fused bias gradient needs a phase-pipelined variant, cout % 4 == 0 "
                            "and a contiguous fp32 (cout,) output")
+    if splits is not None and (splits < 1 or splits > max(1, (g.M + 31) // 32)):
+        raise RuntimeError("conv_wgrad: splits must be between 1 and the number of 32-pixel sub-stages")
+    if variant in _WGRAD_DIRECT:
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != cout * K:
+            raise RuntimeError("conv_wgrad: the direct form writes a contiguous fp32 (cout, K) gradient")
+        _chk(lib().mxr_conv_wgrad_pipe_direct(_p(x), _p(dy), ldy, _p(out), _p(sc), int(accumulate),
+                                              _p(zero_page(dy.device)), ctypes.byref(g), _WGRAD_DIRECT[variant][1],
+                                              _s()), "conv_wgrad_pipe_direct")
+        return out
     if variant in _WGRAD_P8:
-        splits = _splits_pipe(g, 256, 256)
+        splits = splits or _splits_pipe(g, 256, 256)
         nb = 0 if bias_out is None else splits * cout
         part = torch.empty(splits * cout * K + nb, dtype=torch.float32, device=dy.device)
         _chk(lib().mxr_conv_wgrad_p8_bias(_p(x), _p(dy), ldy, _p(part), splits, _p(out), _p(sc), int(accumulate),
@@ -90,14 +127,14 @@ def conv_wgrad(x, dy, g: ConvGeom, scale: Optional[torch.Tensor], out: Optional[
         return out
     if variant in _WGRAD_PIPE_TILE:
         tk, tc = _WGRAD_PIPE_TILE[variant]
-        splits = _splits_pipe(g, tk, tc, _WGRAD_PIPE_OCC.get(variant, 1))
+        splits = splits or _splits_pipe(g, tk, tc, _WGRAD_PIPE_OCC.get(variant, 1))
         part = torch.empty(splits * cout * K, dtype=torch.float32, device=dy.device)
         _chk(lib().mxr_conv_wgrad_pipe(_p(x), _p(dy), ldy, _p(part), splits, _p(out), _p(sc), int(accumulate),
                                        _p(zero_page(dy.device)), ctypes.byref(g), variant - 3, _s()),
              "conv_wgrad_pipe")
         return out
     bk, bco = _WGRAD_TILE[variant]
-    splits = _splits(g, bk, bco)
+    splits = splits or _splits(g, bk, bco)
     part = torch.empty(splits * cout * K, dtype=torch.float32, device=dy.device)
     _chk(_bind().mxr_conv_wgrad(_p(x), _p(dy), ldy, _p(part), splits, _p(out), _p(sc), int(accumulate),
                                 _p(zero_page(dy.device)), ctypes.byref(g), variant, _s()), "conv_wgrad")
@@ -106,7 +143,7 @@ def conv_wgrad(x, dy, g: ConvGeom, scale: Optional[torch.Tensor], out: Optional[
 def wgrad_candidates(x, dy, g, scale, only: Optional[str] = None):
     if only is not None:
         return _only_wgrad(only, x, dy, g, scale, None)
-    vs = list(_WGRAD_TILE) + list(_WGRAD_PIPE_TILE) + list(_WGRAD_P8)
+    vs = _wgrad_variants(g)
     c = {"hip%d" % v: (lambda v=v: conv_wgrad(x, dy, g, scale, variant=v)) for v in vs}
     if w64_covers(g):
         c["w64"] = lambda: wgrad3x3_c64(x, dy, scale)
@@ -122,7 +159,8 @@ def _only_wgrad(only, x, dy, g, scale, sink):
     global _WGRAD_VS
     if _WGRAD_VS is None:
         _WGRAD_VS = set(list(_WGRAD_TILE) + list(_WGRAD_PIPE_TILE) + list(_WGRAD_P8))
-    if only.startswith("hip") and int(only[3:]) in _WGRAD_VS:
+    if only.startswith("hip") and (int(only[3:]) in _WGRAD_VS or
+                                   (int(only[3:]) in _WGRAD_DIRECT and direct_covers(g))):
         v = int(only[3:])
         if sink is None:
             return {only: lambda: conv_wgrad(x, dy, g, scale, variant=v)}
@@ -355,7 +393,7 @@ def _wgrad_sink_cands(x, dy, g, scale, lib_fn):
             if only == "miopen":
                 return {only: lambda: sink.add_(lib_fn())}
             return _only_wgrad(only, x, dy, g, scale, sink)
-        vs = list(_WGRAD_TILE) + list(_WGRAD_PIPE_TILE) + list(_WGRAD_P8)
+        vs = _wgrad_variants(g)
         c = {"hip%d" % v: (lambda v=v: conv_wgrad(x, dy, g, scale, out=sink, accumulate=True, variant=v)) for v in vs}
         c["miopen"] = lambda: sink.add_(lib_fn())
         if w64_covers(g):

@@ -106,6 +106,7 @@ _SIGS = {
                                c_int, c_vp, c_int, c_vp],
     "mxr_conv_wgrad_pipe": [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp, ctypes.POINTER(ConvGeom), c_int,
                             c_vp],
+    "mxr_conv_wgrad_pipe_direct": [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, ctypes.POINTER(ConvGeom), c_int, c_vp],
     "mxr_flip_transpose": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp],
     "mxr_image_warp_normalize": [c_vp, c_int, c_int, c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_float, c_float,
                                  c_float, c_float, c_float, c_vp],
@@ -428,8 +429,41 @@ class AdamPlan:
             self.hyper[1] = lr
             self._lr = lr
 
+    def sync_iter(self, iteration: int) -> None:
+        """Make the device step counter hold ``iteration`` (a fill only when the host mirror disagrees)."""
+        if self.host_iter != iteration:
+            self.iter.fill_(iteration)
+            self.host_iter = iteration
+
 
 _PLANS = {}
+
+
+class ShapeSlots:
+    """A persistent zero-initialised buffer per shape for rows a kernel only partly writes (the zero-padded
+    gradient rows of the final layers: columns past the real channels are never written and must stay zero).
+    One floating slot, replaced when the shape changes, plus every slot pinned by a captured step graph
+    (``train.step_graphs``): a graph keeps the pointer it was captured with, so that buffer must neither go back
+    to the allocator nor be handed to another shape while the graph lives."""
+
+    def __init__(self):
+        self.cur = None
+        self.pinned = {}
+
+    def get(self, key, make) -> torch.Tensor:
+        t = self.pinned.get(key)
+        if t is not None:
+            return t
+        if self.cur is None or self.cur[0] != key:
+            self.cur = (key, make())
+        return self.cur[1]
+
+    def pin_current(self) -> None:
+        if self.cur is not None:
+            self.pinned[self.cur[0]] = self.cur[1]
+
+    def unpin_all(self) -> None:
+        self.pinned = {}
 
 
 # fp8 head weights requantised by one batched launch per optimizer step (ComputeWeights.hx8_quant); a switch for
@@ -686,8 +720,7 @@ def adam_step(flat, m, v, grad_scale, lr, iteration, b1, b2, eps, plan: Optional
     """Fused Keras-Adam on the flat buffers.  ``lr`` is the base lr (lr_t is computed on device)."""
     plan = plan or adam_plan(flat)
     plan.set_lr(lr)
-    if plan.host_iter != iteration:
-        plan.iter.fill_(iteration)
+    plan.sync_iter(iteration)
     plan.host_iter = iteration + 1
     gs = grad_scale.reshape(1).float().contiguous() if torch.is_tensor(grad_scale) else \
         torch.full((1,), float(grad_scale), device=flat.data.device)

@@ -67,10 +67,13 @@ class Trainer:
         self.shapes_callback = None
         self.last_logs: Dict[str, torch.Tensor] = {}
         self.compute_weights = None
-        self._cls_pad_buf = None
-        self._focal_req = None      # ops.conv_launch.FocalRequest: the classification final's fused focal loss
-        self._reg_pad_buf = None
         from ..ops import native
+        # zero-padded gradient rows of the two final layers: one buffer per shape a captured step holds plus a
+        # floating one (a graph keeps the pointer it was captured with)
+        self._cls_pad_buf = native.ShapeSlots()
+        self._focal_req = None      # ops.conv_launch.FocalRequest: the classification final's fused focal loss
+        self._reg_pad_buf = native.ShapeSlots()
+        self.step_graphs = None     # train.step_graphs.StepGraphs once enable_graphs() ran
         from ..ops import fp8 as _fp8
         _fp8.reset_state()      # process-wide fp8 delayed-scaling state (the packed features) starts per model
         if (self.device.type == "cuda" and compute_dtype == torch.bfloat16 and native.available()
@@ -141,11 +144,8 @@ class Trainer:
                 # smooth-L1 writes d(loss)/d(regression) into the final layer's 64-padded rows (36 -> 64);
                 # the layer's data / weight / bias gradients then read them as is (no pad, cast or slice)
                 key = (reg.shape[0], reg.shape[1] // A, (4 * A + 63) // 64 * 64, reg.device)
-                buf = self._reg_pad_buf
-                if buf is None or buf[0] != key:
-                    buf = (key, torch.zeros(key[:3], dtype=reg.dtype, device=reg.device))
-                    self._reg_pad_buf = buf
-                reg_loss, dpad = native.smooth_l1_fwd_bwd(reg, reg_t, state, npos, grad_out=buf[1], group=A)
+                buf = self._reg_pad_buf.get(key, lambda: torch.zeros(key[:3], dtype=reg.dtype, device=reg.device))
+                reg_loss, dpad = native.smooth_l1_fwd_bwd(reg, reg_t, state, npos, grad_out=buf, group=A)
                 rsink["dy"] = dpad
                 dreg = torch.zeros((), dtype=reg.dtype, device=reg.device).expand(reg.shape)
             else:
@@ -165,11 +165,8 @@ class Trainer:
                 # the focal kernel writes d(loss)/d(logits) straight into the final layer's zero-padded
                 # data-gradient rows; autograd carries a zero-stride placeholder
                 key = (cls.shape[0], cls.shape[1] // A, cp, cls.device)
-                buf = self._cls_pad_buf
-                if buf is None or buf[0] != key:
-                    buf = (key, torch.zeros(key[:3], dtype=cls.dtype, device=cls.device))
-                    self._cls_pad_buf = buf
-                cls_loss, dpad = native.focal_fwd_bwd(cls, state, label, npos, grad_out=buf[1], group=A)
+                buf = self._cls_pad_buf.get(key, lambda: torch.zeros(key[:3], dtype=cls.dtype, device=cls.device))
+                cls_loss, dpad = native.focal_fwd_bwd(cls, state, label, npos, grad_out=buf, group=A)
                 sink["dy"] = dpad
                 dcls = torch.zeros((), dtype=cls.dtype, device=cls.device).expand(cls.shape)
             else:
@@ -197,6 +194,8 @@ class Trainer:
             # (Module.train() walks all ~150 modules: ~0.9 ms of host time, which sat in front of the
             # step's first kernels every step when called unconditionally)
             self.model.train()
+        if self.step_graphs is not None:
+            return self.step_graphs.step(images, gt, gt_count, image_hw)
         return self._train_on_batch(images, gt, gt_count, image_hw)
 
     def _train_on_batch(self, images, gt, gt_count, image_hw):
@@ -234,6 +233,8 @@ class Trainer:
                                "the torch.distributed path runs eagerly")
         if _fp8.enabled():
             raise RuntimeError("graph_step: the fp8 delayed-scaling state advances on the host each step")
+        if self.step_graphs is not None:
+            raise RuntimeError("graph_step: this trainer already replays per-shape-class graphs (enable_graphs)")
         dev = self.device
         static = {"images": images.to(dev).clone(), "gt": gt.to(dev).clone(), "gt_count": gt_count.to(dev).clone(),
                   "image_hw": image_hw.to(dev).clone()}
@@ -269,6 +270,35 @@ class Trainer:
         self._graph = graph
         return replay
 
+    # ---------------------------------------------------------------- per-shape-class step graphs
+    def enable_graphs(self, max_shapes: int = 8, eager_sightings: int = 2):
+        """Route ``train_on_batch`` through a per-shape-class cache of captured steps (``train.step_graphs``):
+        a class's first ``eager_sightings`` batches run eagerly, the next one is captured and from then on replayed;
+        at most ``max_shapes`` classes are captured.  Same conditions as :meth:`graph_step`.  Returns the cache."""
+        from ..ops import fp8 as _fp8
+        from .step_graphs import StepGraphs
+        if self.device.type != "cuda":
+            raise RuntimeError("enable_graphs: HIP graphs need a GPU device")
+        if runtime.distributed() and self.optimizer.native is None:
+            raise RuntimeError("enable_graphs across ranks needs the native RCCL bucket engine (MXR_COMM=auto/native); "
+                               "the torch.distributed path runs eagerly")
+        if _fp8.enabled():
+            raise RuntimeError("enable_graphs: the fp8 delayed-scaling state advances on the host each step")
+        self.step_graphs = StepGraphs(self, max_shapes=max_shapes, eager_sightings=eager_sightings)
+        return self.step_graphs
+
+    def adam_plan(self):
+        """The fused Adam kernel's device tables and host mirrors (None where the torch expression runs)."""
+        from ..ops import native
+        return native.adam_plan(self.flat) if self.base_optimizer._use_hip() else None
+
+    def persistent_slots(self):
+        """Every per-shape persistent buffer a captured step may hold a pointer to."""
+        slots = [self._cls_pad_buf, self._reg_pad_buf]
+        if self._focal_req is not None:
+            slots += [self._focal_req._buf, self._focal_req._qbuf]
+        return slots
+
     # ---------------------------------------------------------------- keras-ish
     @property
     def lr(self) -> float:
@@ -283,6 +313,8 @@ class Trainer:
 
     def on_weights_changed(self) -> None:
         """Call after weights/optimizer state were replaced (broadcast, checkpoint restore)."""
+        if self.step_graphs is not None:
+            self.step_graphs.invalidate()       # the flat buffers are rebound and the compute copies rebuilt
         self.flat.rebind()
         if self.compute_weights is not None:
             self.compute_weights.build()     # BN scales may have changed too

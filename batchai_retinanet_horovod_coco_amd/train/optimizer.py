@@ -81,10 +81,16 @@ class KerasAdam:
         c = self.clipnorm
         return torch.where(norm >= c, c / norm.clamp_min(1e-30), torch.ones_like(norm))
 
-    def lr_t(self, t: int) -> float:
+    def base_lr(self, t: int) -> float:
+        """The learning rate of iteration ``t`` (1-based) before the bias correction, ``decay`` included: what the
+        fused kernel is handed, by the eager step and -- outside the graph -- before every graph replay."""
         lr = self.lr
         if self.decay > 0:
             lr = lr * (1.0 / (1.0 + self.decay * (t - 1)))
+        return lr
+
+    def lr_t(self, t: int) -> float:
+        lr = self.base_lr(t)
         return lr * math.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
 
     def apply(self, grad_scale: torch.Tensor) -> None:
@@ -93,8 +99,7 @@ class KerasAdam:
         lr_t = self.lr_t(t)
         if self._use_hip():
             from ..ops import native
-            lr = self.lr if self.decay <= 0 else self.lr * (1.0 / (1.0 + self.decay * (t - 1)))
-            native.adam_step(self.flat, self.m, self.v, grad_scale, lr, self.iterations, self.beta_1, self.beta_2,
+            native.adam_step(self.flat, self.m, self.v, grad_scale, self.base_lr(t), self.iterations, self.beta_1, self.beta_2,
                              self.epsilon)
         else:
             g = self.flat.grad * grad_scale

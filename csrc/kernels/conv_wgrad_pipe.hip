@@ -57,11 +57,16 @@ __device__ __forceinline__ void vm_wait() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// NS: LDS ring depth (DMA runs NS - 1 sub-stages ahead); 3 shrinks the ring so two blocks share a CU
-template <int TK, int TC, int WK, int WC, int ILV = 0, int NW = 8, int NS = WNST>
-__global__ __launch_bounds__(NW * 64) void conv_wgrad_pipe_kernel(
+// NS: LDS ring depth (DMA runs NS - 1 sub-stages ahead); 3 shrinks the ring so two blocks share a CU.
+// DIRECT: the slab-free form -- one split over the whole pixel range (the caller passes splits = 1), and the
+// epilogue stores out[co, k] = (accumulate ? out : 0) + scale[co] * acc straight from the accumulators (`part` is the
+// gradient itself): wgrad_reduce_kernel's arithmetic at one slab, without the workspace and the second launch.
+// Every output element belongs to exactly one block: deterministic, no atomics.
+template <int TK, int TC, int WK, int WC, int ILV, int NW, int NS, bool DIRECT>
+__device__ __forceinline__ void conv_wgrad_pipe_body(
     const bf16_t* __restrict__ X, const bf16_t* __restrict__ dY, int ldy, float* __restrict__ part,
-    const bf16_t* __restrict__ zpage, ConvGeom g, int tiles_k, int tiles_co, int splits, int nsub) {
+    const bf16_t* __restrict__ zpage, const ConvGeom& g, int tiles_k, int tiles_co, int splits, int nsub,
+    const float* __restrict__ scale, int accumulate) {
   static_assert(WK * WC == NW, "wave grid");
   constexpr int T_BYTES = WR * TC * 2, U_BYTES = WR * TK * 2, STAGE = T_BYTES + U_BYTES;
   constexpr int CPT = TC / 8, CPU = TK / 8;          // 16-B chunks per T / U row
@@ -295,18 +300,46 @@ __global__ __launch_bounds__(NW * 64) void conv_wgrad_pipe_kernel(
   }
 
   // slab write: part[split][co][k]; lane holds k = 4*kg + e (e = 0..3) of co = lane & 15 per tile
+  // (K % 8 == 0 and k % 4 == 0: a lane's four columns are inside K together or not at all)
   float* slab = part + (long long)split * g.cout * K;
 #pragma unroll
   for (int j = 0; j < TJ; ++j) {
     const int co = co0 + wc * WT_CO + j * 16 + (lane & 15);
     if (co >= g.cout) continue;
+    float sc = 1.f;
+    if constexpr (DIRECT) sc = scale ? scale[co] : 1.f;
 #pragma unroll
     for (int i = 0; i < TI; ++i) {
       const int k = k0 + wk * WT_K + i * 16 + 4 * kg;
       if (k >= K) continue;
-      *reinterpret_cast<f32x4*>(slab + (long long)co * K + k) = acc[i][j];
+      f32x4* dst = reinterpret_cast<f32x4*>(slab + (long long)co * K + k);
+      if constexpr (DIRECT) {
+        f32x4 v = acc[i][j];
+        if (scale) v *= sc;
+        if (accumulate) v += *dst;
+        *dst = v;
+      } else {
+        *dst = acc[i][j];
+      }
     }
   }
+}
+
+template <int TK, int TC, int WK, int WC, int ILV = 0, int NW = 8, int NS = WNST>
+__global__ __launch_bounds__(NW * 64) void conv_wgrad_pipe_kernel(
+    const bf16_t* __restrict__ X, const bf16_t* __restrict__ dY, int ldy, float* __restrict__ part,
+    const bf16_t* __restrict__ zpage, ConvGeom g, int tiles_k, int tiles_co, int splits, int nsub) {
+  conv_wgrad_pipe_body<TK, TC, WK, WC, ILV, NW, NS, false>(X, dY, ldy, part, zpage, g, tiles_k, tiles_co, splits, nsub,
+                                                           nullptr, 0);
+}
+
+template <int TK, int TC, int WK, int WC, int ILV = 0, int NW = 8, int NS = WNST>
+__global__ __launch_bounds__(NW * 64) void conv_wgrad_pipe_direct_kernel(
+    const bf16_t* __restrict__ X, const bf16_t* __restrict__ dY, int ldy, float* __restrict__ out,
+    const bf16_t* __restrict__ zpage, ConvGeom g, int tiles_k, int tiles_co, int nsub,
+    const float* __restrict__ scale, int accumulate) {
+  conv_wgrad_pipe_body<TK, TC, WK, WC, ILV, NW, NS, true>(X, dY, ldy, out, zpage, g, tiles_k, tiles_co, 1, nsub, scale,
+                                                          accumulate);
 }
 
 template <int TK, int TC, int WK, int WC, int ILV = 0, int NW = 8, int NS = WNST>
@@ -326,6 +359,27 @@ int launch_wgrad_pipe(const bf16_t* X, const bf16_t* dY, int ldy, float* part, i
     attr_set = true;
   }
   kern<<<(unsigned)nwg, NW * 64, lds, stream>>>(X, dY, ldy, part, zpage, g, tiles_k, tiles_co, splits, (int)nsub);
+  return (int)hipGetLastError();
+}
+
+template <int TK, int TC, int WK, int WC, int ILV = 0, int NW = 8, int NS = WNST>
+int launch_wgrad_pipe_direct(const bf16_t* X, const bf16_t* dY, int ldy, float* out, const float* scale,
+                             int accumulate, const bf16_t* zpage, const ConvGeom& g, hipStream_t stream) {
+  const int K = g.kh * g.kw * g.cin;
+  const int tiles_k = (K + TK - 1) / TK;
+  const int tiles_co = (g.cout + TC - 1) / TC;
+  const long long nsub = (g.M + WR - 1) / WR;
+  if (nsub > 0x7fffffffLL) return -4;
+  const long long nwg = (long long)tiles_k * tiles_co;
+  const size_t lds = (size_t)NS * WR * (TK + TC) * 2 + 6 * MXR_MAXLEV * sizeof(int);
+  auto kern = conv_wgrad_pipe_direct_kernel<TK, TC, WK, WC, ILV, NW, NS>;
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr_set = true;
+  }
+  kern<<<(unsigned)nwg, NW * 64, lds, stream>>>(X, dY, ldy, out, zpage, g, tiles_k, tiles_co, (int)nsub, scale,
+                                                accumulate);
   return (int)hipGetLastError();
 }
 
@@ -367,4 +421,22 @@ MXR_API int mxr_conv_wgrad_pipe(const void* X, const void* dY, int ldy, float* p
   const int K = g->kh * g->kw * g->cin;
   mxr_wgrad_reduce_launch(part, splits, (long long)g->cout * K, K, scale, out, accumulate, stream);
   return (int)hipGetLastError();
+}
+
+// The slab-free weight gradient (DIRECT form): no workspace, no reduce launch; out (cout x K fp32) is written or
+// accumulated into by the GEMM's epilogue.  variant 0: 128 k x 128 co (the tile of pipe variant 10), 1: 64 x 64
+// (pipe variant 9).  For small-M weight gradients whose tile count alone fills a useful grid (one image: the
+// stage-5 and FPN P6 / P7 layers).  (A 128 k x 64 co tile was slower than both on every swept layer.)
+MXR_API int mxr_conv_wgrad_pipe_direct(const void* X, const void* dY, int ldy, float* out, const float* scale,
+                                       int accumulate, const void* zpage, const ConvGeom* g, int variant,
+                                       hipStream_t stream) {
+  if (g->cin % 8 != 0 || ldy % 8 != 0 || g->ostride != 1) return -1;
+  if (g->nlev < 1 || g->nlev > MXR_MAXLEV) return -2;
+  if (g->M + 64 >= (1LL << 31)) return -4;
+  const bf16_t *x = (const bf16_t*)X, *dy = (const bf16_t*)dY, *z = (const bf16_t*)zpage;
+  switch (variant) {
+    case 0: return launch_wgrad_pipe_direct<128, 128, 2, 4, 1, 8>(x, dy, ldy, out, scale, accumulate, z, *g, stream);
+    case 1: return launch_wgrad_pipe_direct<64, 64, 2, 2, 0, 4>(x, dy, ldy, out, scale, accumulate, z, *g, stream);
+    default: return -3;
+  }
 }
