@@ -5,18 +5,16 @@ weights, 1x1 / stride-2 as a strided scatter, 3x3 / stride-2 as the four sub-pix
 from __future__ import annotations
 
 import ctypes
-import os
-from typing import Optional, Sequence, Tuple
+import functools
+from typing import Optional, Tuple
 
 import torch
-import torch.nn.functional as F
 
 from . import native as _n
-from .native import ConvGeom, _chk, _p, _s, lib, zero_page, c_int, c_ll, c_vp
-from .side_stream import SIDE
+from .native import _chk, _p, _s, lib, zero_page
 from . import conv_launch as _cl
-from .conv_launch import (C1X1_BN, FWD_VARIANTS, HALO_VARIANTS, HX32_NARROW, HX32_VARIANTS, P8_TUNED, BitMask, _only, bits_capable, flip, geom_single, hip_conv_ok, launch_fwd, relu_bwd, torch_conv_backward)
-
+from .conv_launch import (BitMask, _bits_filter, _only, flip, geom_single, hip_conv_ok, launch_fwd, relu_bwd,
+                          torch_conv_backward)
 
 def conv_dgrad(dy, w, x_shape, stride, pads, variant: Optional[int] = None, mask: Optional[torch.Tensor] = None,
                out: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
@@ -26,30 +24,36 @@ def conv_dgrad(dy, w, x_shape, stride, pads, variant: Optional[int] = None, mask
     ``res`` (stride 1): dX = dgrad + res into a fresh tensor (``out`` without touching ``res``).
     1x1/s2 with ``out``: only the strided positions are read, accumulated and masked -- the buffer it
     joins is the other 1x1/s2 branch's fresh dX, which already holds zeros at the gaps."""
-    N, H, W, cin = x_shape
-    cout, kh, kw, _ = w.shape
-    Ho, Wo = dy.shape[1], dy.shape[2]
-    if stride == 1 and hip_conv_ok(cout, cin, dy.dtype):
-        wd = flip(w)
-        dpads = (kh - 1 - pads[0], kh - 1 - pads[1], kw - 1 - pads[2], kw - 1 - pads[3])
-        dx = out if out is not None else torch.empty((N, H, W, cin), dtype=dy.dtype, device=dy.device)
-        launch_fwd(dy, wd, None, res, dx, geom_single(N, Ho, Wo, H, W, kh, 1, dpads, cout, cin), False,
-                   accumulate=out is not None, variant=variant, mask=mask)
-        return dx
-    if res is not None:
+    form, g = dgrad_geom(dy.shape, w.shape, x_shape, stride, pads)
+    if form is None or not hip_conv_ok(w.shape[0], x_shape[3], dy.dtype) or (res is not None and form != "s1"):
         return None
-    if kh == 1 and stride == 2 and tuple(pads) == (0, 0, 0, 0) and hip_conv_ok(cout, cin, dy.dtype):
-        wd = flip(w)     # 1x1: the flip is the (cin, cout) transpose
-        # the kernels write the zeros of the positions no output pixel maps to themselves (when not
-        # accumulating), so a fresh dX needs no fill pass
-        dx = out if out is not None else torch.empty((N, H, W, cin), dtype=dy.dtype, device=dy.device)
-        g = geom_single(N, Ho, Wo, Ho, Wo, 1, 1, (0, 0, 0, 0), cout, cin, ostride=2, oH=H, oW=W)
-        launch_fwd(dy, wd, None, None, dx, g, False, accumulate=out is not None, variant=variant, mask=mask)
-        return dx
-    if kh == 3 and kw == 3 and stride == 2 and hip_conv_ok(cout, cin, dy.dtype):
+    if form == "subpixel":
         assert not isinstance(mask, BitMask), "mxr_s2_shuffle reads a bf16 mask"
         return _dgrad_s2_subpixel(dy, w, x_shape, pads, variant, mask, out)
-    return None
+    # ("scatter": the flip of a 1x1 is the (cin, cout) transpose; the kernels write the zeros of the positions no
+    # output pixel maps to themselves (when not accumulating), so a fresh dX needs no fill pass)
+    dx = out if out is not None else torch.empty(tuple(x_shape), dtype=dy.dtype, device=dy.device)
+    launch_fwd(dy, flip(w), None, res, dx, g, False, accumulate=out is not None, variant=variant, mask=mask)
+    return dx
+
+def dgrad_geom(dy_shape, w_shape, x_shape, stride, pads):
+    """(form, geometry) of the forward launch over dY that computes this data gradient, or (None, None) where
+    no HIP form covers it.  "s1": stride 1, the forward of the flipped weights; "scatter": 1x1 / stride 2, a
+    1x1 forward whose output is scattered over the stride grid; "subpixel": 3x3 / stride 2, the 2x2 forward of
+    the four stacked phases (:func:`_dgrad_s2_subpixel`)."""
+    N, H, W, cin = x_shape
+    cout, kh, kw, _ = w_shape
+    Ho, Wo = dy_shape[1], dy_shape[2]
+    if stride == 1:
+        dpads = (kh - 1 - pads[0], kh - 1 - pads[1], kw - 1 - pads[2], kw - 1 - pads[3])
+        return "s1", geom_single(N, Ho, Wo, H, W, kh, 1, dpads, cout, cin)
+    if kh == 1 and stride == 2 and tuple(pads) == (0, 0, 0, 0):
+        return "scatter", geom_single(N, Ho, Wo, Ho, Wo, 1, 1, (0, 0, 0, 0), cout, cin, ostride=2, oH=H, oW=W)
+    if kh == 3 and kw == 3 and stride == 2:
+        win = _s2_taps(tuple(pads))[1]
+        return "subpixel", geom_single(N, Ho, Wo, (H + 1) // 2, (W + 1) // 2, 2, 1, (win[0], 0, win[1], 0), cout,
+                                       4 * cin)
+    return None, None
 
 def _s2_phase_taps(p: int, pad: int):
     """Sub-pixel split of a 3-tap / stride-2 data gradient along one axis: input coordinate i = 2a + p
@@ -75,11 +79,9 @@ def _dgrad_s2_subpixel(dy, w, x_shape, pads, variant, mask, out):
     all phases; ``mxr_s2_shuffle`` scatters them into dX with the mask / accumulation.  (1.8x the MACs of
     the exact phases, but one launch instead of four small ones.)"""
     N, H, W, cin = x_shape
-    cout = w.shape[0]
-    Ho, Wo = dy.shape[1], dy.shape[2]
     Hp, Wp = (H + 1) // 2, (W + 1) // 2
-    w4, win = _s2_stacked_weights_hip(w, pads)
-    g = geom_single(N, Ho, Wo, Hp, Wp, 2, 1, (win[0], 0, win[1], 0), cout, 4 * cin)
+    w4, _ = _s2_stacked_weights_hip(w, pads)
+    g = dgrad_geom(dy.shape, w.shape, x_shape, 2, pads)[1]
     y4 = torch.empty((N, Hp, Wp, 4 * cin), dtype=dy.dtype, device=dy.device)
     launch_fwd(dy, w4, None, None, y4, g, False, variant=variant)
     dx = out if out is not None else torch.empty((N, H, W, cin), dtype=dy.dtype, device=dy.device)
@@ -106,18 +108,19 @@ def _s2_stack_taps(pads):
                     taps.append(-1 if ky is None or kx is None else ky * 3 + kx)
     return taps, (pty, ptx)
 
-_S2_TAPS = {}
+@functools.lru_cache(maxsize=None)
+def _s2_taps(pads):
+    """:func:`_s2_stack_taps` per pads tuple, the taps as the kernels' ``int[16]`` (dispatch asks on every call)."""
+    taps, win = _s2_stack_taps(pads)
+    return (ctypes.c_int * 16)(*taps), win
+
 # stacked stride-2 weights as row copies of the batched flip (a switch for same-process A/Bs)
 S2_FROM_FLIP = True
 
 def _s2_stacked_weights_hip(w, pads):
     """_s2_stacked_weights in one kernel (mxr_s2_stack) instead of ~25 small torch ops."""
     cout, _, _, cin = w.shape
-    key = (tuple(pads), w.device)
-    ent = _S2_TAPS.get(key)
-    if ent is None:
-        taps, win = _s2_stack_taps(pads)
-        ent = _S2_TAPS[key] = ((ctypes.c_int * 16)(*taps), win)
+    ent = _s2_taps(tuple(pads))
     w4 = torch.empty((4 * cin, 2, 2, cout), dtype=w.dtype, device=w.device)
     cw = _n.compute_weights()
     wd = cw.flipped(w) if cw is not None else None
@@ -160,46 +163,33 @@ def _s2_stacked_weights(w, pads):
             blocks.append(torch.stack(rows, 1))              # (cin, 2, 2, cout)
     return torch.cat(blocks, 0).contiguous(), (pty, ptx)
 
+@functools.lru_cache(maxsize=4096)
+def _hip_names(dy_shape, w_shape, x_shape, stride, pads, dtype, narrow):
+    """Names of the HIP forms raced for one data gradient: the forward families' names for its geometry, less
+    what conv_launch.DGRAD_* leave out.  Cached per layer shape (building the geometry and asking every family is
+    ~15 us of host time per call); ``narrow``: conv_launch.NARROW_TILES, which the names depend on."""
+    form, g = dgrad_geom(dy_shape, w_shape, x_shape, stride, pads)
+    cin = x_shape[3]
+    if form is None or not hip_conv_ok(w_shape[0], cin, dtype):
+        return ()
+    names = _cl.offered(g, _cl.DGRAD_ORDER if form == "s1" else _cl.DGRAD_S2_ORDER, _cl.DGRAD_SKIP)
+    if form == "subpixel" and cin % 8:      # hipN from 3: 16-B chunks of dX's cin, not of the stacked 4 cin
+        names = [n for n in names if int(n[3:]) < 3]
+    return tuple(names)
+
 def _dgrad_cands(dy, w, x, stride, pads, mask=None, out=None, res=None, only: Optional[str] = None):
-    cands = {}
-    cout, kh = w.shape[0], w.shape[1]
-    cin = x.shape[-1]
-    if res is not None:
-        assert out is None and stride == 1
-        kw = dict(mask=mask, res=res)
-    else:
-        kw = dict(mask=mask, out=out)
-    if only is not None and (only.startswith("hip") or only.startswith("c1x1_") or only.startswith("p8_")
-                             or only.startswith("halo") or only.startswith("hx32_") or only == "c1p"):
-        # the tuned winner among the HIP forms: every one of them is conv_dgrad with that variant
-        v = int(only[3:]) if only.startswith("hip") else only
-        return {only: (lambda: conv_dgrad(dy, w, tuple(x.shape), stride, pads, v, **kw))}
-    if (stride == 1 or (kh == 1 and stride == 2 and tuple(pads) == (0, 0, 0, 0))
-            or (kh == 3 and w.shape[2] == 3 and stride == 2)) and hip_conv_ok(cout, cin, dy.dtype):
-        for v in FWD_VARIANTS:
-            if v < 3 or cin % 8 == 0:
-                cands["hip%d" % v] = (lambda v=v: conv_dgrad(dy, w, tuple(x.shape), stride, pads, v, **kw))
-        if stride == 1 and kh == 1 and tuple(pads) == (0, 0, 0, 0) and cout in (64, 128, 256) and cin % 8 == 0:
-            for bn in C1X1_BN:
-                if bn * cout <= 32768 and bn <= max(64, cin):
-                    cands["c1x1_%d" % bn] = (lambda bn=bn: conv_dgrad(dy, w, tuple(x.shape), stride, pads,
-                                                                      "c1x1_%d" % bn, **kw))
-        if (stride == 1 and kh == 1 and tuple(pads) == (0, 0, 0, 0) and cout % 32 == 0 and cout >= 96
-                and cin % 8 == 0 and cin >= 64):
-            # the persistent streaming 1x1 kernel (conv1x1_pers.hip) on the transposed weights
-            cands["c1p"] = lambda: conv_dgrad(dy, w, tuple(x.shape), stride, pads, "c1p", **kw)
-        if stride == 1 and cout % 64 == 0 and cin % 8 == 0 and kh * w.shape[2] <= 16:
-            for v in ["p8_%d" % v for v in P8_TUNED]:
-                cands[v] = (lambda v=v: conv_dgrad(dy, w, tuple(x.shape), stride, pads, v, **kw))
-        if stride == 1 and kh == 3 and tuple(pads) == (1, 1, 1, 1) and cout % 32 == 0 and cin % 8 == 0:
-            for v in HALO_VARIANTS:
-                cands["halo%d" % v] = (lambda v=v: conv_dgrad(dy, w, tuple(x.shape), stride, pads, "halo%d" % v,
-                                                              **kw))
-            for v in HX32_VARIANTS:
-                if v in HX32_NARROW and (cin > 64 or not _cl.NARROW_TILES):   # 64-channel tiles: narrow outputs
-                    continue
-                cands["hx32_%d" % v] = (lambda v=v: conv_dgrad(dy, w, tuple(x.shape), stride, pads, "hx32_%d" % v,
-                                                               **kw))
+    cout, cin = w.shape[0], x.shape[-1]
+    assert res is None or (out is None and stride == 1)
+
+    def hip(name):       # every HIP form is conv_dgrad with that variant
+        return lambda: conv_dgrad(dy, w, tuple(x.shape), stride, pads, name, mask=mask, out=out, res=res)
+    fam = _cl.family_of(only) if only is not None else None
+    if fam is not None and fam.prefix in _cl.DGRAD_ORDER:
+        # the tuned winner among the HIP forms (checked by family only: a coverage check would build the
+        # geometry on every call, host time the backward pass does not have)
+        return {only: hip(only)}
+    cands = {n: hip(n) for n in _hip_names(dy.shape, w.shape, x.shape, stride, tuple(pads), dy.dtype,
+                                           _cl.NARROW_TILES)}
 
     from . import fp8 as _f8
     if (_f8.enabled() and stride == 1 and res is None and _f8.dgrad_eligible(cout, cin)
@@ -207,10 +197,8 @@ def _dgrad_cands(dy, w, x, stride, pads, mask=None, out=None, res=None, only: Op
         # fp8 data gradient (conv_p8_f8's e5m2 x e4m3 form; quantisation of dY and of the flipped weights
         # included in the timed candidate, so the tuner keeps it only where it wins)
         N, H, W, _ = x.shape
-        k_h, k_w = w.shape[1], w.shape[2]
-        dpads = (k_h - 1 - pads[0], k_h - 1 - pads[1], k_w - 1 - pads[2], k_w - 1 - pads[3])
-        g8 = geom_single(N, dy.shape[1], dy.shape[2], H, W, k_h, 1, dpads, cout, cin)
-        g8.kw = k_w
+        g8 = dgrad_geom(dy.shape, w.shape, x.shape, 1, pads)[1]
+        g8.kw = w.shape[2]
 
         def f8_dgrad(v):
             # (lean: one delayed-scaling pass over dY, the flipped 3x3 weights from the per-step batched quantisation;
@@ -254,17 +242,12 @@ def run_dgrad(dy, w, x, stride, pads, mask: Optional[torch.Tensor] = None,
     key = TUNER.key("dgrad", N, H, W, cin, cout, kh, stride, tuple(pads)) + \
         ("|mb" if bits else "|m" if mask is not None else "") + ("|a" if (out is not None or res is not None) else "")
     only = _only(key)
-    cands = _dgrad_cands(dy, w, x, stride, pads, mask, out, res, only=only) if only is not None else None
-    if bits and cands:
-        cands = {k: v for k, v in cands.items() if bits_capable(k)}
+    cands = _bits_filter(_dgrad_cands(dy, w, x, stride, pads, mask, out, res, only=only), mask) if only is not None else None
     if not cands:
-        cands = _dgrad_cands(dy, w, x, stride, pads, mask, out, res)
-        if bits:
-            cands = {k: v for k, v in cands.items() if bits_capable(k)}
+        cands = _bits_filter(_dgrad_cands(dy, w, x, stride, pads, mask, out, res), mask)
     if out is not None and TUNER.needs_tuning(key, cands):
         # time the accumulating candidates against a scratch copy, then run the winner for real
-        tc = _dgrad_cands(dy, w, x, stride, pads, mask, out.clone())
-        TUNER.run(key, {k: v for k, v in tc.items() if bits_capable(k)} if bits else tc)
+        TUNER.run(key, _bits_filter(_dgrad_cands(dy, w, x, stride, pads, mask, out.clone()), mask))
     return TUNER.run(key, cands)
 
 

@@ -1,19 +1,21 @@
 """Convolution kernel launchers, geometry and the forward candidate sets (split out of ``native_conv``).
 
-One function per HIP kernel family -- ``conv_igemm.hip`` / ``conv_pipe.hip`` (``launch_fwd``),
-``conv_p8.hip``, ``conv1x1_stream.hip``, ``conv_halo.hip``, ``conv_hx32.hip`` -- with the shape checks the
-kernels assume, the library (MIOpen) forms, and ``fwd_candidates`` / ``run_fwd``: the tuned forward of the
-conv layers the reference builds at /root/reference/train.py:91.
+One function per HIP kernel family -- ``conv_igemm.hip`` / ``conv_pipe.hip`` (``launch_hip``), ``conv_p8.hip``,
+``conv1x1_stream.hip``, ``conv_halo.hip``, ``conv_hx32.hip`` -- with the shape checks the kernels assume, ``FAMILIES``
+(the one table of them: names, launcher, BitMask flag), the library (MIOpen) forms, and ``fwd_candidates`` /
+``run_fwd``: the tuned forward of the conv layers the reference builds at /root/reference/train.py:91.
 """
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
-from typing import Optional, Sequence, Tuple
+from typing import Callable, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
 
+from . import halo as _hx
 from . import native as _n
 from .native import ConvGeom, _chk, _p, _s, lib, zero_page, c_int, c_ll, c_vp
 from .side_stream import SIDE
@@ -118,54 +120,23 @@ class BitMask:
 
 MASK_BITS = os.environ.get("MXR_MASK_BITS", "1") == "1"
 
-def bits_capable(name: str) -> bool:
-    """Tuner candidates whose epilogue handles a :class:`BitMask` (conv_pipe, split-K pipe, streaming 1x1,
-    halo and hx32 kernels; not the igemm hip0-2 / p8 direct epilogues, MIOpen or fp8)."""
-    if name.startswith(("c1x1_", "sk", "halo", "hx32_")) or name == "c1p":
-        return True
-    return name.startswith("hip") and name[3:].isdigit() and int(name[3:]) >= 3
+FWD_VARIANTS = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16)
+_IGEMM_VARIANTS = tuple(v for v in FWD_VARIANTS if v < 3)      # the pipe kernels (from 3) store 16-B chunks: cout % 8
 
-def _bits_filter(cands, mask):
-    if not isinstance(mask, BitMask):
-        return cands
-    return {k: v for k, v in cands.items() if bits_capable(k)}
-
-def launch_fwd(x, w, bias, res, y, g: ConvGeom, relu: bool, accumulate: bool = False,
-               variant: Optional[int] = None, mask: Optional[torch.Tensor] = None) -> None:
-    """One implicit-GEMM launch.  ``mask``: zero the output where ``mask <= 0`` (fused relu backward
-    of the layer that produced this conv's input); ``accumulate``: ``y += result``."""
-    v = _variant(g.cout) if variant is None else variant
+def launch_hip(x, w, bias, res, y, g: ConvGeom, relu: bool, accumulate: bool = False, variant: int = 0,
+               mask: Optional[torch.Tensor] = None) -> None:
+    """One implicit-GEMM launch of ``hipN``: 0-2 = the igemm tiles (conv_igemm.hip); from 3 the deep-pipelined 8-wave
+    kernels (conv_pipe.hip): 3 = 256co x 256pix, 4 = 128co x 256pix, 5 / 6 = the same with the next sub-stage's DMA
+    interleaved between MFMA groups, 7 / 8 = interleaved + s_setprio around the MFMA groups, 9 / 10 = narrow 64co x
+    256pix on 4 waves (two blocks per CU; 64-channel layers), 10 with s_setprio; 11 / 12 / 13 = 128-pixel tiles (128 /
+    256 / 64 co) for the small-K 1x1 layers whose epilogue (residual / mask / accumulate) dominates; 14 / 15 / 16 =
+    3-deep LDS rings (128x128, 64x128, 128x256: 3 / 4 / 2 blocks per CU)."""
     zp = _p(zero_page(x.device))
-    if isinstance(v, str) and v.startswith("c1x1_"):   # streaming narrow-K 1x1 kernel (conv1x1_stream.hip)
-        launch_c1x1(x, w, bias, res, y, g, relu, accumulate, int(v[5:]), mask)
-        return
-    if v == "c1p":      # persistent streaming 1x1 kernel (conv1x1_pers.hip)
-        launch_c1p(x, w, bias, res, y, g, relu, accumulate, mask)
-        return
-    if isinstance(v, str) and v.startswith("hx32_"):   # 32x32x16-MFMA halo kernel (conv_hx32.hip)
-        launch_hx32(x, w, bias, res, y, g, relu, accumulate, int(v[5:]), mask)
-        return
-    if isinstance(v, str) and v.startswith("sk"):    # split-K form of the 128-pixel pipe tiles (conv_pipe.hip)
-        launch_splitk(x, w, bias, res, y, g, relu, accumulate, int(v[2:]), mask)
-        return
-    if isinstance(v, str) and v.startswith("p8_"):   # 256x256 kernels, 8-wave phases (conv_p8.hip)
-        launch_p8(x, w, bias, res, y, g, relu, accumulate, int(v[3:]), mask)
-        return
-    if isinstance(v, str):      # "haloN": halo-staged 3x3/s1 kernel (conv_halo.hip, tile table ops/halo.py)
-        launch_halo(x, w, bias, res, y, g, relu, accumulate, int(v[4:]), mask)
-        return
-    if v >= 3:   # deep-pipelined 8-wave kernels (conv_pipe.hip): 3 = 256co x 256pix, 4 = 128co x 256pix,
-                 # 5 / 6 = the same with the next sub-stage's DMA interleaved between MFMA groups,
-                 # 7 / 8 = interleaved + s_setprio around the MFMA groups,
-                 # 9 / 10 = narrow 64co x 256pix on 4 waves (two blocks per CU; 64-channel layers),
-                 # 10 with s_setprio; 11 / 12 / 13 = 128-pixel tiles (128 / 256 / 64 co) for the
-                 # small-K 1x1 layers whose epilogue (residual / mask / accumulate) dominates;
-                 # 14 / 15 / 16 = 3-deep LDS rings (128x128, 64x128, 128x256: 3 / 4 / 2 blocks per CU)
-        _chk(lib().mxr_conv_fwd_pipe(_p(x), _p(w), _p(bias), _p(res), _p(mask), _p(y), zp, ctypes.byref(g),
-                                     int(relu), int(accumulate), v - 3, _s()), "conv_fwd_pipe")
-        return
+    if variant >= 3:
+        return _chk(lib().mxr_conv_fwd_pipe(_p(x), _p(w), _p(bias), _p(res), _p(mask), _p(y), zp, ctypes.byref(g),
+                                            int(relu), int(accumulate), variant - 3, _s()), "conv_fwd_pipe")
     _chk(lib().mxr_conv_fwd(_p(x), _p(w), _p(bias), _p(res), _p(mask), _p(y), zp, ctypes.byref(g), int(relu),
-                            int(accumulate), v, _s()), "conv_fwd")
+                            int(accumulate), variant, _s()), "conv_fwd")
 
 HALO_VARIANTS = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15)
 
@@ -176,8 +147,10 @@ HX32_NARROW = (8, 9)     # the 64-channel tiles: offered only to layers with cou
 NARROW_TILES = True      # (a switch for same-process A/Bs, scripts/bench_switch.py; not an environment knob)
 
 
+_HX32_WIDE = tuple(v for v in HX32_VARIANTS if v not in HX32_NARROW)
+
 def hx32_variants(g: ConvGeom):
-    return tuple(v for v in HX32_VARIANTS if v not in HX32_NARROW or (g.cout <= 64 and NARROW_TILES))
+    return HX32_VARIANTS if g.cout <= 64 and NARROW_TILES else _HX32_WIDE
 
 C1X1_BN = (64, 128, 256)
 
@@ -196,9 +169,7 @@ def p8_covers(g: ConvGeom) -> bool:
             and (int(g.M) + 1) * max(g.cin, g.cout) < 2 ** 31 and g.cout * K < 2 ** 31)
 
 def big_tile_variants(g: ConvGeom):
-    if not p8_covers(g):
-        return []
-    return ["p8_%d" % v for v in P8_TUNED]
+    return ["p8_%d" % v for v in P8_TUNED] if p8_covers(g) else []
 
 def launch_p8(x, w, bias, res, y, g: ConvGeom, relu: bool, accumulate: bool = False, variant: int = 0,
               mask: Optional[torch.Tensor] = None) -> None:
@@ -294,7 +265,6 @@ def launch_halo(x, w, bias, res, y, g: ConvGeom, relu: bool, accumulate: bool = 
                 mask: Optional[torch.Tensor] = None) -> None:
     """3x3 / stride-1 / pad-1 conv with halo-staged pixels (csrc/kernels/conv_halo.hip): per 32-channel
     chunk each tile's input halo is loaded into LDS once and shared by the 9 taps."""
-    from . import halo as _hx
     if not _hx.covers(g):
         raise RuntimeError("conv3x3_halo: geometry not covered")
     tiles, nt = _hx.device_tiles(_hx.geom_batch(g), _hx.geom_shapes(g), x.device)
@@ -306,7 +276,6 @@ def launch_hx32(x, w, bias, res, y, g: ConvGeom, relu: bool, accumulate: bool = 
                 mask: Optional[torch.Tensor] = None) -> None:
     """3x3 / stride-1 / pad-1 conv on the 32x32x16 MFMA (variants 10-15: the 16x16x32 MFMA) with plane-split LDS
     images (csrc/kernels/conv_hx32.hip; same tile table as :func:`launch_halo`)."""
-    from . import halo as _hx
     if not hx32_covers(g):
         raise RuntimeError("conv3x3_hx32: geometry not covered")
     if not (x.is_contiguous() and w.is_contiguous() and y.is_contiguous() and x.shape[-1] == g.cin
@@ -365,7 +334,6 @@ FOCAL_VARIANTS = (0, 10)      # conv_hx32 tiles with the fused focal form (10: t
 def launch_hx32_focal(x, w, bias, g: ConvGeom, req: "FocalRequest", ld: int, variant: int = 0) -> torch.Tensor:
     """conv_hx32 variant ``variant`` (:data:`FOCAL_VARIANTS`) with the focal loss in its epilogue: returns the padded
     gradient rows [N, P, ld] (also the loss into ``req.loss``)."""
-    from . import halo as _hx
     from .losses import LOGIT_HI, LOGIT_LO
     N = int(g.M) // g.out_img
     C = g.cout // req.A
@@ -407,8 +375,89 @@ def hx32_packed(w: torch.Tensor, cout: int, cin: int) -> torch.Tensor:
     return wp
 
 def hx32_covers(g: ConvGeom) -> bool:
-    from . import halo as _hx
     return _hx.covers(g) and g.cout * 9 * g.cin * 2 < 2 ** 31
+
+# ------------------------------------------------------------------------------- the kernel families
+
+class Family(NamedTuple):
+    """One forward kernel family.  Its candidate names are ``prefix`` + a variant number (``c1p``: the prefix
+    alone); the tuner stores them and tuning/conv_table.json pins them."""
+    prefix: str
+    names: Callable      # (g: ConvGeom) -> the names offered for that geometry, in race order
+    launch: Callable     # (x, w, bias, res, y, g, relu, accumulate, name, mask)
+    bits: object         # the epilogue takes a :class:`BitMask`: a bool, or a predicate of the name
+
+def _numbered(prefix: str, fn):
+    """The launcher ``fn`` (variant as an int) as a table launcher (a[8]: the candidate name, a[9]: the mask)."""
+    n = len(prefix)
+    return lambda *a: fn(*a[:8], int(a[8][n:]), a[9])
+
+@functools.lru_cache(maxsize=None)
+def _named(prefix: str, variants) -> Tuple[str, ...]:
+    """The candidate names of a tuple of variant numbers (cached: dispatch asks on every call)."""
+    return tuple("%s%d" % (prefix, v) for v in variants)
+
+# A new forward family is its launcher plus one entry here (and its prefix in the race orders below).
+FAMILIES = (
+    # conv_igemm.hip / conv_pipe.hip (launch_hip); only the pipe epilogues (N >= 3) take a BitMask
+    Family("hip", lambda g: _named("hip", FWD_VARIANTS if g.cout % 8 == 0 else _IGEMM_VARIANTS),
+           _numbered("hip", launch_hip), lambda name: name[3:].isdigit() and int(name[3:]) >= 3),
+    # halo-staged 3x3 / s1 kernel (conv_halo.hip, tile table ops/halo.py), and its 32x32x16-MFMA form (conv_hx32.hip)
+    Family("halo", lambda g: _named("halo", HALO_VARIANTS) if _hx.covers(g) else (), _numbered("halo", launch_halo), True),
+    Family("hx32_", lambda g: _named("hx32_", hx32_variants(g)) if hx32_covers(g) else (),
+           _numbered("hx32_", launch_hx32), True),
+    # streaming narrow-K 1x1 kernel (conv1x1_stream.hip), and the persistent one (conv1x1_pers.hip: no variant number)
+    Family("c1x1_", c1x1_variants, _numbered("c1x1_", launch_c1x1), True),
+    Family("c1p", lambda g: ("c1p",) if c1p_covers(g) else (), lambda *a: launch_c1p(*a[:8], a[9]), True),
+    # 256x256 kernels, 8-wave phases (conv_p8.hip): a direct epilogue, no BitMask
+    Family("p8_", big_tile_variants, _numbered("p8_", launch_p8), False),
+    # split-K form of the 128-pixel pipe tiles (conv_pipe.hip)
+    Family("sk", lambda g: _named("sk", tuple(v for v in SK_VARIANTS if splitk_splits(g, v))),
+           _numbered("sk", launch_splitk), True),
+)
+_FAMILY = {f.prefix: f for f in FAMILIES}
+
+# The order in which each pass lists its families.  It is part of the tuning: the first listed candidate runs
+# under graph capture and with MXR_CONV_TUNE=0, the race goes in this order and exact ties keep the earlier name.
+FWD_ORDER = ("hip", "halo", "hx32_", "c1x1_", "c1p", "p8_", "sk")
+# A data gradient is the forward of its own geometry (ops.conv_dgrad.dgrad_geom) and races that geometry's forward
+# names, except what it has never raced (no table entry or recorded timing holds one; offering them is a tuning
+# change): the split-K forms, ``c1x1_65``, and for the two stride-2 forms (scatter, sub-pixel) all but ``hip``.
+DGRAD_ORDER = ("hip", "c1x1_", "c1p", "p8_", "halo", "hx32_")
+DGRAD_S2_ORDER = ("hip",)
+DGRAD_SKIP = ("c1x1_65",)
+
+def family_of(name: str) -> Optional[Family]:
+    """The family of a candidate name (None: not a forward HIP kernel -- ``miopen``, fp8, unknown)."""
+    return _FAMILY.get(name.rstrip("0123456789"))
+
+def offered(g: ConvGeom, order=FWD_ORDER, skip=()):
+    """Candidate names of the families ``order`` for ``g``, in race order, without the names ``skip``."""
+    return [n for p in order for n in _FAMILY[p].names(g) if n not in skip]
+
+def bits_capable(name: str) -> bool:
+    """Tuner candidates whose epilogue handles a :class:`BitMask` (conv_pipe, split-K pipe, streaming 1x1,
+    halo and hx32 kernels; not the igemm hip0-2 / p8 direct epilogues, MIOpen or fp8)."""
+    bits = getattr(family_of(name), "bits", False)
+    return bits(name) if callable(bits) else bits
+
+def _bits_filter(cands, mask):
+    if not isinstance(mask, BitMask):
+        return cands
+    return {k: v for k, v in cands.items() if bits_capable(k)}
+
+def launch_fwd(x, w, bias, res, y, g: ConvGeom, relu: bool, accumulate: bool = False,
+               variant=None, mask: Optional[torch.Tensor] = None) -> None:
+    """One forward launch of ``variant``: a candidate name of :data:`FAMILIES`, or an integer N for ``hipN``
+    (None: the default igemm tile).  ``mask``: zero the output where ``mask <= 0`` (fused relu backward
+    of the layer that produced this conv's input); ``accumulate``: ``y += result``."""
+    v = _variant(g.cout) if variant is None else variant
+    if not isinstance(v, str):
+        return launch_hip(x, w, bias, res, y, g, relu, accumulate, v, mask)
+    fam = family_of(v)
+    if fam is None:
+        raise RuntimeError("launch_fwd: %r names no kernel family" % (v,))
+    fam.launch(x, w, bias, res, y, g, relu, accumulate, v, mask)
 
 def relu_bwd_(dy: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     """In-place ``dy *= (y > 0)`` (elementwise: reading and writing the same element is safe)."""
@@ -439,8 +488,6 @@ def miopen_fwd(x, w, bias, res, stride, pads, relu):
     if not y.is_contiguous():
         y = y.contiguous()
     return bias_res_act_(y, bias, res, relu)
-
-FWD_VARIANTS = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16)
 
 # output target of the next forward launch (the HIP candidates write there instead of a fresh tensor): a chunk of a
 # preallocated full-batch activation (ResidualBlockFn's image-chunked forward); see :func:`run_fwd_into`
@@ -484,59 +531,26 @@ def fwd_candidates(x, w, b, res, g: ConvGeom, stride, pads, relu, out_shape, all
             launch_fwd(x, w, b, res, y, g, relu, variant=v, mask=mask)
             return y
         return f
-    if only is not None:
-        return _bits_filter(_only_fwd(only, hip, g, out, allow_miopen, f8c, x, w, b, res, stride, pads, relu, mask),
-                            mask)
-    cands = {"hip%d" % v: hip(v) for v in FWD_VARIANTS if v < 3 or g.cout % 8 == 0}
-    from . import halo as _hx
-    if _hx.covers(g):
-        cands.update({"halo%d" % v: hip("halo%d" % v) for v in HALO_VARIANTS})
-    if hx32_covers(g):
-        cands.update({"hx32_%d" % v: hip("hx32_%d" % v) for v in hx32_variants(g)})
-    cands.update({v: hip(v) for v in c1x1_variants(g)})
-    if c1p_covers(g):
-        cands["c1p"] = hip("c1p")
-    cands.update({v: hip(v) for v in big_tile_variants(g)})
-    cands.update({"sk%d" % v: hip("sk%d" % v) for v in SK_VARIANTS if splitk_splits(g, v)})
+    def library():
+        y = miopen_fwd(x, w, b, res, stride, pads, relu)
+        return y if mask is None else relu_bwd(y, mask)
     if out is not None:       # accumulating forms: HIP kernels only (their epilogue adds in place)
         allow_miopen = False
         f8c = {}
-    if allow_miopen:
-        if mask is None:
-            cands["miopen"] = lambda: miopen_fwd(x, w, b, res, stride, pads, relu)
+    if only is not None:      # empty when ``only`` is not a candidate of this call: the caller builds the full set
+        fam = family_of(only)
+        if fam is not None:
+            cands = {only: hip(only)} if only in fam.names(g) else {}
+        elif only == "miopen":
+            cands = {only: library} if allow_miopen else {}
         else:
-            cands["miopen"] = lambda: relu_bwd(miopen_fwd(x, w, b, res, stride, pads, relu), mask)
+            cands = {only: f8c[only]} if only in f8c else {}
+        return _bits_filter(cands, mask)
+    cands = {name: hip(name) for name in offered(g)}
+    if allow_miopen:
+        cands["miopen"] = library
     cands.update(f8c)
     return _bits_filter(cands, mask)
-
-def _only_fwd(only, hip, g, out, allow_miopen, f8c, x, w, b, res, stride, pads, relu, mask):
-    """fwd_candidates restricted to ``only`` (empty when it is not a candidate of this call: the caller
-    then builds the full set)."""
-    if only.startswith("hip"):
-        v = int(only[3:])
-        return {only: hip(v)} if v in FWD_VARIANTS and (v < 3 or g.cout % 8 == 0) else {}
-    if only.startswith("hx32_"):
-        return {only: hip(only)} if hx32_covers(g) and int(only[5:]) in hx32_variants(g) else {}
-    if only.startswith("halo"):
-        from . import halo as _hx
-        return {only: hip(only)} if _hx.covers(g) and int(only[4:]) in HALO_VARIANTS else {}
-    if only.startswith("c1x1_"):
-        return {only: hip(only)} if only in c1x1_variants(g) else {}
-    if only == "c1p":
-        return {only: hip(only)} if c1p_covers(g) else {}
-    if only.startswith("p8_"):
-        return {only: hip(only)} if only in big_tile_variants(g) else {}
-    if only.startswith("sk"):
-        return {only: hip(only)} if int(only[2:]) in SK_VARIANTS and splitk_splits(g, int(only[2:])) else {}
-    if only == "miopen":
-        if out is not None or not allow_miopen:
-            return {}
-        if mask is None:
-            return {only: lambda: miopen_fwd(x, w, b, res, stride, pads, relu)}
-        return {only: lambda: relu_bwd(miopen_fwd(x, w, b, res, stride, pads, relu), mask)}
-    if out is None and only in f8c:
-        return {only: f8c[only]}
-    return {}
 
 def _only(key: str) -> Optional[str]:
     """The tuned winner for ``key`` when dispatch can go straight to it (else None: build every candidate).

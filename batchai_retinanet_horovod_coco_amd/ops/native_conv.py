@@ -26,12 +26,12 @@ from .native import ConvGeom, _chk, _p, _s, lib, zero_page, c_int, c_ll, c_vp
 from .side_stream import SIDE
 from .conv_launch import (  # noqa: F401  (re-exported: the public surface of native_conv)
     MASK_BITS, BitMask, bits_capable, proj_fusable, run_fwd_proj, run_fwd_into, C1X1_BN, FWD_VARIANTS, HALO_VARIANTS, HX32_VARIANTS, P8_TUNED, P8_VARIANTS, _BOUND, _SIGS, _bind,
-    _effective, _miopen_pyramid_wgrad, _miopen_wgrad, _only, _only_fwd, _out_hw, _variant, bias_res_act_,
-    big_tile_variants, c1x1_variants, flip, fwd_candidates, geom_pyramid, geom_single, hip_conv_ok,
+    _effective, _miopen_pyramid_wgrad, _miopen_wgrad, _only, _out_hw, _variant, bias_res_act_,
+    big_tile_variants, c1x1_variants, family_of, flip, fwd_candidates, geom_pyramid, geom_single, hip_conv_ok,
     hx32_covers, hx32_packed, launch_c1x1, launch_fwd, launch_halo, launch_hx32, launch_p8, miopen_fwd,
     p8_covers, relu_bwd, relu_bwd_, run_fwd, torch_conv_backward,)
 from .conv_dgrad import (  # noqa: F401  (re-exported: the public surface of native_conv)
-    proj_dgrad_fusable, run_dgrad_proj, _S2_TAPS, _dgrad_cands, _dgrad_s2_subpixel, _pick_taps, _s2_phase_taps, _s2_stack_taps,
+    proj_dgrad_fusable, run_dgrad_proj, _dgrad_cands, _dgrad_s2_subpixel, _pick_taps, _s2_phase_taps, _s2_stack_taps,
     _s2_stacked_weights, _s2_stacked_weights_hip, conv_dgrad, run_dgrad,)
 from .conv_wgrad import (  # noqa: F401  (re-exported: the public surface of native_conv)
     proj_wgrad_fusable, run_wgrad_proj, _WGRAD_P8, _WGRAD_PIPE_OCC, _WGRAD_PIPE_TILE, _WGRAD_TILE, _WGRAD_VS, _WH_TILES, _deliver_wgrad,

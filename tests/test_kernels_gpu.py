@@ -415,3 +415,52 @@ def test_conv_splitk_matches_fp32(cuda, variant, case, epi):
         CL.launch_fwd(x, w, b, res, y, g, True, variant=variant)
     err = (y.float() - ref).abs().max().item() / (ref.abs().max().item() + 1e-3)
     assert err < 2e-2, err
+
+
+@pytest.mark.parametrize("name", ["hip0", "hip3", "halo0", "hx32_0", "hx32_8", "c1x1_64", "c1p", "p8_5", "sk11"])
+def test_launch_fwd_dispatches_by_family_name(cuda, name):
+    """``launch_fwd(variant=name)`` runs the launcher of the name's family (conv_launch.FAMILIES): the same bits as
+    that launcher called directly (``hipN``: as the integer form), on every 9x9 geometry that offers the name.
+    No kernel of its own: it pins the name-to-launcher map."""
+    from batchai_retinanet_horovod_coco_amd.ops import conv_launch as CL
+    direct = {
+        "hip": lambda *a, v, m: CL.launch_fwd(*a, variant=v, mask=m),
+        "halo": lambda *a, v, m: CL.launch_halo(*a, v, m),
+        "hx32_": lambda *a, v, m: CL.launch_hx32(*a, v, m),
+        "c1x1_": lambda *a, v, m: CL.launch_c1x1(*a, v, m),
+        "c1p": lambda *a, v, m: CL.launch_c1p(*a, m),
+        "p8_": lambda *a, v, m: CL.launch_p8(*a, v, m),
+        "sk": lambda *a, v, m: CL.launch_splitk(*a, v, m),
+    }
+    fam = CL.family_of(name)
+    number = int(name[len(fam.prefix):]) if name != fam.prefix else None
+    ran = 0
+    for cin, cout, k, p in [(64, 64, 3, 1), (128, 64, 1, 0)]:
+        g = CL.geom_single(1, 9, 9, 9, 9, k, 1, (p, p, p, p), cin, cout)
+        if name not in fam.names(g):
+            continue
+        torch.manual_seed(11)
+        x = torch.randn(1, 9, 9, cin, device=cuda).bfloat16()
+        w = (torch.randn(cout, k, k, cin, device=cuda) / (k * k * cin) ** 0.5).bfloat16()
+        b = torch.randn(cout, device=cuda)
+        y0 = torch.zeros(1, 9, 9, cout, device=cuda, dtype=torch.bfloat16)
+        y1 = torch.zeros_like(y0)
+        CL.launch_fwd(x, w, b, None, y0, g, True, variant=name)
+        direct[fam.prefix](x, w, b, None, y1, g, True, False, v=number, m=None)
+        ref = ref_conv(x, w, b, 1, (p, p, p, p), True)
+        assert torch.equal(y0, y1), (name, k)
+        assert (y0.float() - ref).abs().max().item() / (ref.abs().max().item() + 1e-3) < 2e-2
+        ran += 1
+    assert ran, name
+
+
+@pytest.mark.parametrize("name", ["nope", "nope0", "hx", "c1x1", "miopen", "f8_0"])
+def test_launch_fwd_rejects_unknown_names(cuda, name):
+    """A string that names no family raises (it used to fall through to the halo launcher)."""
+    from batchai_retinanet_horovod_coco_amd.ops import conv_launch as CL
+    g = CL.geom_single(1, 9, 9, 9, 9, 3, 1, (1, 1, 1, 1), 64, 64)
+    x = torch.zeros(1, 9, 9, 64, device=cuda, dtype=torch.bfloat16)
+    w = torch.zeros(64, 3, 3, 64, device=cuda, dtype=torch.bfloat16)
+    y = torch.zeros(1, 9, 9, 64, device=cuda, dtype=torch.bfloat16)
+    with pytest.raises(RuntimeError, match="names no kernel family"):
+        CL.launch_fwd(x, w, None, None, y, g, False, variant=name)
