@@ -9,7 +9,8 @@ Same subcommands, flags, defaults and argument checks as ``/root/reference/train
 ``--image-max-side``), plus a ``synthetic`` dataset and MI355X options (``--dtype``, ``--clip-mode``,
 ``--bucket-mb``, ``--allreduce-dtype``, ``--workers``, ``--shard-data``, ``--checkpoint-format``,
 ``--lr``, ``--clipnorm``, ``--seed``, ``--log-every``, ``--no-metric-average``, ``--log-all-ranks``,
-``--metrics-jsonl``, ``--stop-on-nan``, ``--graph``, ``--graph-shapes``).
+``--metrics-jsonl``, ``--stop-on-nan``, ``--graph``, ``--graph-shapes``, ``--eval-batch-size``,
+``--eval-pad-multiple``, ``--eval-workers``).
 
 Orchestration follows ``main()`` (``train.py:383-450``): init the data-parallel runtime
 (``hvd.init()``), backbone object, generators, model (snapshot or weights), summary, callbacks
@@ -121,6 +122,14 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--no-snapshots", help="Disable saving snapshots.", dest="snapshots", action="store_false")
     parser.add_argument("--no-evaluation", help="Disable per epoch evaluation.", dest="evaluation",
                         action="store_false")
+    parser.add_argument("--eval-batch-size", type=int, default=0,
+                        help="Evaluate in batches of this many images, sharded over all ranks (eval/batched.py). "
+                             "Default 0: the per-image evaluation on rank 0, as the reference does it.")
+    parser.add_argument("--eval-pad-multiple", type=int, default=0,
+                        help="With --eval-batch-size: pad evaluation batches to a multiple of this, so images of "
+                             "different sizes share a batch.  Default 0: a batch holds one exact resized shape.")
+    parser.add_argument("--eval-workers", type=int, default=4,
+                        help="With --eval-batch-size: threads that decode evaluation images ahead of the GPU.")
     parser.add_argument("--freeze-backbone", help="Freeze training of backbone layers.", action="store_true")
     parser.add_argument("--random-transform", help="Randomly transform image and annotations.", action="store_true")
     parser.add_argument("--image-min-side", help="Rescale the image so the smallest side is min_side.", type=int,
@@ -257,10 +266,12 @@ def create_callbacks(trainer, prediction_model, validation_generator, args):
                                               batch_size=args.batch_size, write_graph=True)
         callbacks.append(tensorboard_callback)
     if args.evaluation and validation_generator:
+        batched = dict(batch_size=args.eval_batch_size, pad_multiple=args.eval_pad_multiple,
+                       workers=args.eval_workers)
         if args.dataset_type == "coco":
-            evaluation = CocoEval(validation_generator, tensorboard=tensorboard_callback)
+            evaluation = CocoEval(validation_generator, tensorboard=tensorboard_callback, **batched)
         else:
-            evaluation = Evaluate(validation_generator, tensorboard=tensorboard_callback)
+            evaluation = Evaluate(validation_generator, tensorboard=tensorboard_callback, **batched)
         callbacks.append(kc.RedirectModel(evaluation, prediction_model))
     if args.metrics_jsonl and rank == 0:
         callbacks.append(kc.JSONLMetrics(args.metrics_jsonl, every=args.log_every, batch_size=args.batch_size,

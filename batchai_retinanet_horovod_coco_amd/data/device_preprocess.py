@@ -63,6 +63,64 @@ class DevicePreprocessor:
             native.image_resize_into(f, batch, i, (oh, ow))
         return batch
 
+    # ------------------------------------------------------------------ evaluation batches
+    def _stage(self, images: List[np.ndarray]):
+        """Pack the uint8 images into one of two pinned host buffers and start ONE async copy to the device.
+        The buffers alternate; the event recorded after a buffer's copy is waited for before that buffer is
+        written again, so a copy that may still be in flight never reads a half-refilled buffer."""
+        st = getattr(self, "_staging", None)
+        if st is None:
+            st = self._staging = {"next": 0, "host": [None, None], "event": [None, None]}
+        offsets, total = [], 0
+        for im in images:
+            offsets.append(total)
+            total += im.shape[0] * im.shape[1] * 3
+        k = st["next"]
+        st["next"] = k ^ 1
+        if st["event"][k] is not None:
+            st["event"][k].synchronize()
+        cuda = self.device.type == "cuda"
+        host = st["host"][k]
+        if host is None or host.numel() < total:
+            host = st["host"][k] = torch.empty(max(total, 1), dtype=torch.uint8, pin_memory=cuda)
+        view = host.numpy()
+        for im, off in zip(images, offsets):
+            n = im.shape[0] * im.shape[1] * 3
+            view[off:off + n] = np.ascontiguousarray(im, dtype=np.uint8).reshape(-1)
+        dev = torch.empty(max(total, 1), dtype=torch.uint8, device=self.device)
+        dev[:total].copy_(host[:total], non_blocking=True)
+        if cuda:
+            if st["event"][k] is None:
+                st["event"][k] = torch.cuda.Event()
+            st["event"][k].record()
+        return dev, offsets
+
+    def build_eval_batch(self, images: List[np.ndarray], batch_size: int):
+        """The evaluation batch of ``images`` (uint8 BGR HWC), built by one kernel launch per 32 slots.
+
+        Returns ``(batch, sizes, scales)``: ``batch`` is ``(batch_size, Hm, Wm, 3)`` with image i normalised and
+        resized (``resize_image`` sizes) at the top-left of slot i and zeros elsewhere, ``(Hm, Wm)`` the largest
+        resized size padded to ``pad_multiple``; ``sizes[i]`` is image i's resized ``(oh, ow)`` and ``scales[i]`` its
+        resize scale.  The kernel writes every value of the batch, so nothing is zero-filled first and no
+        full-size fp32 image is materialised."""
+        from ..ops import native
+        from .generator import pad_shape
+        if not 1 <= len(images) <= batch_size:
+            raise ValueError("build_eval_batch: {} images for {} slots".format(len(images), batch_size))
+        sizes, scales = [], []
+        for im in images:
+            if im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("build_eval_batch wants HWC images with 3 channels, got {}".format(im.shape))
+            (oh, ow), s = self.output_size(im.shape[:2])
+            sizes.append((oh, ow))
+            scales.append(s)
+        Hm, Wm = pad_shape((max(s[0] for s in sizes), max(s[1] for s in sizes)), self.pad_multiple)
+        staging, offsets = self._stage(images)
+        table = [(off, im.shape[0], im.shape[1], oh, ow) for off, im, (oh, ow) in zip(offsets, images, sizes)]
+        batch = torch.empty((batch_size, Hm, Wm, 3), dtype=self.dtype, device=self.device)
+        native.image_batch_resize_normalize(staging, table, batch, len(images), self.scale, self.mean)
+        return batch, sizes, scales
+
 
 def compute_input_output_device(gen, group) -> Dict[str, torch.Tensor]:
     """``Generator.compute_input_output`` with the image work on the device (see module doc)."""

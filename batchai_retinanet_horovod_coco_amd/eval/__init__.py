@@ -1,1 +1,2 @@
-"""Evaluation: COCO bbox COCOeval re-implementation, VOC-style mAP, evaluation callbacks."""
+"""Evaluation: COCO bbox COCOeval re-implementation, VOC-style mAP, evaluation callbacks, and the batched,
+rank-sharded detection collection behind ``--eval-batch-size`` (``batched.py``)."""

@@ -233,8 +233,56 @@ def predict_image(generator, prediction_model, index: int, device=None):
     return boxes, scores[0].float().cpu().numpy(), labels[0].cpu().numpy()
 
 
+def _run_cocoeval(generator, results, image_ids, results_path, verbose):
+    """Write the two JSON files and compute the 12 stats (``None`` without a single detection)."""
+    if not results:
+        return None
+    path = results_path or "{}_bbox_results.json".format(generator.set_name)
+    with open(path, "w") as f:
+        json.dump(results, f, indent=4)
+    with open("{}_processed_image_ids.json".format(path.replace("_bbox_results.json", "")), "w") as f:
+        json.dump(image_ids, f, indent=4)
+    coco_pred = load_results(generator.coco, results)
+    ev = COCOeval(generator.coco, coco_pred, "bbox")
+    ev.params.imgIds = image_ids
+    ev.evaluate()
+    ev.accumulate()
+    ev.summarize(verbose)
+    return ev.stats
+
+
+def _evaluate_coco_batched(generator, prediction_model, threshold, results_path, verbose, batch_size, pad_multiple,
+                           workers):
+    """``evaluate_coco`` over batches, on all ranks (eval/batched.py): every rank runs its share and receives all
+    detections; rank 0 alone writes the files and runs COCOeval, and its stats (or ``None``) go to every rank."""
+    from ..parallel import collectives
+    from . import batched
+    local = batched.collect_detections(generator, prediction_model, batch_size, pad_multiple, workers, threshold)
+    dets = batched.gather_detections(local, generator.size())
+    stats = None
+    if batched._world()[0] == 0:
+        results, image_ids = [], []
+        for index in range(generator.size()):
+            boxes, scores, labels = dets[index]
+            xywh = np.array(boxes, dtype=np.float32)
+            xywh[:, 2] -= xywh[:, 0]
+            xywh[:, 3] -= xywh[:, 1]
+            image_id = generator.image_ids[index]
+            cats = [generator.label_to_coco_label(int(v)) for v in labels]
+            results.extend({"image_id": image_id, "category_id": c, "score": s, "bbox": b} for c, s, b in
+                           zip(cats, scores.astype(np.float64).tolist(), xywh.astype(np.float64).tolist()))
+            image_ids.append(image_id)
+        stats = _run_cocoeval(generator, results, image_ids, results_path, verbose)
+    return collectives.broadcast_object(stats, 0)
+
+
 def evaluate_coco(generator, prediction_model, threshold: float = 0.05, results_path: Optional[str] = None,
-                  verbose: bool = True):
+                  verbose: bool = True, batch_size: int = 0, pad_multiple: int = 0, workers: int = 4):
+    """``batch_size = 0``: the per-image loop on the calling rank.  ``batch_size >= 1``: batched and sharded over
+    the ranks -- a collective, every rank must call it, and every rank gets the stats."""
+    if batch_size:
+        return _evaluate_coco_batched(generator, prediction_model, threshold, results_path, verbose, int(batch_size),
+                                      pad_multiple, workers)
     results, image_ids = [], []
     for index in range(generator.size()):
         boxes, scores, labels = predict_image(generator, prediction_model, index)

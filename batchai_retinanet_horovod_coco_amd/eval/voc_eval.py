@@ -23,11 +23,12 @@ def _compute_ap(recall: np.ndarray, precision: np.ndarray) -> float:
     return float(np.sum((mrec[i + 1] - mrec[i]) * mpre[i + 1]))
 
 
-def _get_detections(generator, prediction_model, score_threshold=0.05, max_detections=100):
+def _get_detections(generator, prediction_model, score_threshold=0.05, max_detections=100, predicted=None):
+    """``predicted``: ``{image index: (boxes, scores, labels)}`` from eval/batched.py instead of per-image runs."""
     from .coco_eval import predict_image
     all_detections = [[None for _ in range(generator.num_classes())] for _ in range(generator.size())]
     for i in range(generator.size()):
-        boxes, scores, labels = predict_image(generator, prediction_model, i)
+        boxes, scores, labels = predicted[i] if predicted is not None else predict_image(generator, prediction_model, i)
         indices = np.where(scores > score_threshold)[0]
         sc = scores[indices]
         order = np.argsort(-sc)[:max_detections]
@@ -92,7 +93,22 @@ def evaluate_detections(all_detections, all_annotations, num_classes: int,
 
 
 def evaluate(generator, prediction_model, iou_threshold: float = 0.5, score_threshold: float = 0.05,
-             max_detections: int = 100, save_path=None) -> Dict[int, Tuple[float, float]]:
+             max_detections: int = 100, save_path=None, batch_size: int = 0, pad_multiple: int = 0,
+             workers: int = 4) -> Dict[int, Tuple[float, float]]:
+    """``batch_size >= 1``: detections come from eval/batched.py, sharded over the ranks (a collective: every rank
+    calls, rank 0 matches, every rank gets the result); the ``score > threshold`` / top-``max_detections`` rule
+    stays here on the host."""
+    if batch_size:
+        from ..parallel import collectives
+        from . import batched
+        local = batched.collect_detections(generator, prediction_model, int(batch_size), pad_multiple, workers,
+                                           score_threshold)
+        predicted = batched.gather_detections(local, generator.size())
+        aps = None
+        if batched._world()[0] == 0:
+            dets = _get_detections(generator, None, score_threshold, max_detections, predicted=predicted)
+            aps = evaluate_detections(dets, _get_annotations(generator), generator.num_classes(), iou_threshold)
+        return collectives.broadcast_object(aps, 0)
     dets = _get_detections(generator, prediction_model, score_threshold, max_detections)
     anns = _get_annotations(generator)
     return evaluate_detections(dets, anns, generator.num_classes(), iou_threshold)

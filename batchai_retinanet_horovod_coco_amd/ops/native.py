@@ -111,6 +111,9 @@ _SIGS = {
     "mxr_image_warp_normalize": [c_vp, c_int, c_int, c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_float, c_float,
                                  c_float, c_float, c_float, c_vp],
     "mxr_image_resize_into": [c_vp, c_int, c_int, c_vp, c_int, c_int, c_ll, c_int, c_vp],
+    "mxr_image_batch_resize_normalize": [c_vp, c_ll, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_float, c_float,
+                                         c_float, c_float, c_vp],
+    "mxr_detections_finish": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float, c_vp, c_vp, c_vp],
     "mxr_fp8_amax": [c_vp, c_ll, c_vp, c_vp],
     "mxr_fp8_quant": [c_vp, c_ll, c_vp, c_vp, c_vp, c_vp],
     "mxr_fp8_quant_rows": [c_vp, c_int, c_int, c_vp, c_vp, c_vp],
@@ -944,6 +947,65 @@ def filter_detections_batched(anchors: torch.Tensor, deltas: torch.Tensor, cls_l
     return boxes, top_s, labels
 
 
+FINISH_SLOTS = 32
+
+
+def finish_detections_host(boxes, scores, labels, table, threshold: float):
+    """The formula of ``finish_detections`` in numpy fp32 -- its oracle, and the CPU path of eval/batched.py.
+
+    Row d of image b is ``[x1, y1, x2, y2, score, label]``: the box clamped to x in [0, ow], y in [0, oh]
+    (``box_ops.clip_boxes`` bounds, for the image's own resized size) then divided by ``float32(scale)``, as
+    ``predict_image`` divides; ``count[b]`` is the length of the leading run of rows with score >= threshold."""
+    import numpy as np
+    boxes = np.asarray(boxes, dtype=np.float32)
+    scores = np.asarray(scores, dtype=np.float32)
+    table = np.asarray(table, dtype=np.float32).reshape(-1, 3)
+    B, D = scores.shape
+    zero = np.float32(0)
+    oh, ow, sc = table[:, 0:1], table[:, 1:2], table[:, 2:3]
+    rows = np.empty((B, D, 6), dtype=np.float32)
+    for j, hi in ((0, ow), (1, oh), (2, ow), (3, oh)):
+        rows[:, :, j] = np.minimum(np.maximum(boxes[:, :, j], zero), hi) / sc
+    rows[:, :, 4] = scores
+    rows[:, :, 5] = np.asarray(labels).astype(np.float32)
+    below = ~(scores >= np.float32(threshold))
+    count = np.where(below.any(axis=1), below.argmax(axis=1), D).astype(np.int32)
+    return rows, count
+
+
+def finish_detections(boxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, table, threshold: float,
+                      packed: bool = False):
+    """Clip to each image's own size, undo the resize scale and count the rows above ``threshold`` for a batch of
+    ``filter_detections_batched`` outputs (csrc/kernels/detect.hip, formula: :func:`finish_detections_host`).
+
+    boxes (B, D, 4) fp32, scores (B, D) fp32, labels (B, D) int32; ``table`` B rows ``(oh, ow, scale)``.  Returns
+    ``rows (B, D, 6)`` fp32 and ``count (B)`` int32, two views of ONE allocation; ``packed=True`` returns that flat
+    fp32 allocation (rows, then the counts' bits) so the caller brings a batch to the host in one copy."""
+    import numpy as np
+    B, D = int(scores.shape[0]), int(scores.shape[1])
+    assert boxes.dtype == torch.float32 and scores.dtype == torch.float32 and labels.dtype == torch.int32
+    assert tuple(boxes.shape) == (B, D, 4) and tuple(labels.shape) == (B, D)
+    tab = np.ascontiguousarray(np.asarray(table, dtype=np.float32).reshape(-1, 3))
+    if tab.shape[0] != B:
+        raise ValueError("finish_detections: {} table rows for {} images".format(tab.shape[0], B))
+    boxes, scores, labels = boxes.contiguous(), scores.contiguous(), labels.contiguous()
+    flat = torch.empty(B * D * 6 + B, dtype=torch.float32, device=scores.device)
+    rows = flat[:B * D * 6].view(B, D, 6)
+    count = flat[B * D * 6:].view(torch.int32)
+    for b0 in range(0, B, FINISH_SLOTS):
+        n = min(FINISH_SLOTS, B - b0)
+        _chk(lib().mxr_detections_finish(_p(boxes[b0:]), _p(scores[b0:]), _p(labels[b0:]),
+                                         tab[b0:b0 + n].ctypes.data, n, D, float(threshold), _p(rows[b0:]),
+                                         _p(count[b0:]), _s()), "detections_finish")
+    return flat if packed else (rows, count)
+
+
+def unpack_detections(flat, B: int, D: int):
+    """Host side of ``finish_detections(packed=True)``: numpy ``rows (B, D, 6)`` and ``count (B)``."""
+    a = flat.cpu().numpy()
+    return a[:B * D * 6].reshape(B, D, 6), a[B * D * 6:].view("int32")
+
+
 # =========================================================================================
 # device image preprocessing (data/device_preprocess.py)
 # =========================================================================================
@@ -977,6 +1039,34 @@ def image_resize_into(src: torch.Tensor, batch: torch.Tensor, index: int, out_hw
     dt = {torch.float32: 0, torch.bfloat16: 1}[batch.dtype]
     _chk(lib().mxr_image_resize_into(_p(src), int(src.shape[0]), int(src.shape[1]), _p(batch[index]), OH, OW,
                                      int(batch.shape[2]) * 3, dt, _s()), "image_resize")
+
+
+BATCH_SLOTS = 32
+
+
+def image_batch_resize_normalize(staging: torch.Tensor, table, batch: torch.Tensor, n_images: int,
+                                 scale: float = 1.0, mean=(0.0, 0.0, 0.0)) -> None:
+    """Fill the whole ``(B, Hm, Wm, 3)`` fp32 / bf16 ``batch`` from uint8 BGR HWC images packed in ``staging``.
+
+    ``table``: ``n_images`` rows ``(byte offset, H, W, OH, OW)``.  Slot i receives image i as ``x*scale - mean``
+    resized (cv2 INTER_LINEAR) to OH x OW at its top-left and zeros elsewhere; slots >= ``n_images`` are zero, so
+    ``batch`` may come from ``torch.empty``.  One launch per 32 slots (csrc/kernels/image.hip)."""
+    import numpy as np
+    assert staging.dtype == torch.uint8 and staging.is_contiguous() and staging.device == batch.device
+    assert batch.dim() == 4 and batch.shape[3] == 3 and batch.is_contiguous()
+    B, Hm, Wm = int(batch.shape[0]), int(batch.shape[1]), int(batch.shape[2])
+    n_images = int(n_images)
+    tab = np.ascontiguousarray(np.asarray(table, dtype=np.int64).reshape(-1, 5))
+    if tab.shape[0] != n_images or n_images > B:
+        raise ValueError("image_batch_resize_normalize: {} table rows, {} images, {} slots".format(tab.shape[0],
+                                                                                                  n_images, B))
+    dt = _dt(batch)
+    for b0 in range(0, B, BATCH_SLOTS):
+        nb = min(BATCH_SLOTS, B - b0)
+        n = max(0, min(nb, n_images - b0))
+        _chk(lib().mxr_image_batch_resize_normalize(_p(staging), int(staging.numel()), tab[b0:].ctypes.data, n,
+                                                    _p(batch[b0:]), nb, Hm, Wm, dt, float(scale), float(mean[0]),
+                                                    float(mean[1]), float(mean[2]), _s()), "image_batch")
 
 
 # =========================================================================================

@@ -89,6 +89,40 @@ __global__ __launch_bounds__(256) void nms_reduce_kernel(const unsigned long lon
 __global__ void zero_count_kernel(int* c) {
   if (threadIdx.x == 0) c[0] = 0;
 }
+
+// ---- evaluation: finish a batch of filtered detections on the device ----
+constexpr int kMaxFinishSlots = 32;
+struct FinishTable { float oh[kMaxFinishSlots], ow[kMaxFinishSlots], scale[kMaxFinishSlots]; };
+
+// One block per image.  Row d of the image becomes [x1, y1, x2, y2, score, label]: the box clamped to the image's own
+// resized size (x to [0, ow], y to [0, oh], the bounds of box_ops.clip_boxes) and then divided by the resize scale
+// (IEEE fp32 division, what ``boxes / scale`` does on the host).  count = length of the leading run of rows
+// with score >= thr (rows arrive sorted by score, padded with -1).
+__global__ __launch_bounds__(kBlock) void detections_finish_kernel(const float* __restrict__ boxes,
+                                                                   const float* __restrict__ scores,
+                                                                   const int* __restrict__ labels, FinishTable tab, int D,
+                                                                   float thr, float* __restrict__ rows,
+                                                                   int* __restrict__ count) {
+  __shared__ int first_below;
+  const int b = blockIdx.x;
+  const float oh = tab.oh[b], ow = tab.ow[b], sc = tab.scale[b];
+  if (threadIdx.x == 0) first_below = D;
+  __syncthreads();
+  int mine = D;
+  for (int d = threadIdx.x; d < D; d += kBlock) {
+    const long long i = (long long)b * D + d;
+    const float4 bx = reinterpret_cast<const float4*>(boxes)[i];
+    const float s = scores[i];
+    float2* o = reinterpret_cast<float2*>(rows + i * 6);
+    o[0] = make_float2(__fdiv_rn(fminf(fmaxf(bx.x, 0.f), ow), sc), __fdiv_rn(fminf(fmaxf(bx.y, 0.f), oh), sc));
+    o[1] = make_float2(__fdiv_rn(fminf(fmaxf(bx.z, 0.f), ow), sc), __fdiv_rn(fminf(fmaxf(bx.w, 0.f), oh), sc));
+    o[2] = make_float2(s, (float)labels[i]);
+    if (!(s >= thr)) mine = min(mine, d);
+  }
+  if (mine < D) atomicMin(&first_below, mine);
+  __syncthreads();
+  if (threadIdx.x == 0) count[b] = first_below;
+}
 }  // namespace
 
 MXR_API int mxr_decode_clip(const float* anchors, const void* deltas, int dtype, float* boxes, int B, int A, float std_,
@@ -113,4 +147,19 @@ MXR_API int mxr_nms(const float* boxes, int n, float thr, int max_out, unsigned 
   if (lds > 64 * 1024) return -2;
   nms_reduce_kernel<<<1, 256, lds, stream>>>(mask, n, words, max_out, keep, nkeep);
   return (int)hipGetLastError();
+}
+
+// boxes (B, D, 4) fp32, scores (B, D) fp32, labels (B, D) int32 -> rows (B, D, 6) fp32, count (B) int32.
+// table: B rows {oh, ow, scale} fp32 in HOST memory (copied into the launch).  At most 32 images per call.
+MXR_API int mxr_detections_finish(const float* boxes, const float* scores, const int* labels, const float* table, int B,
+                                  int D, float thr, float* rows, int* count, hipStream_t stream) {
+  if (B <= 0 || B > kMaxFinishSlots || D <= 0) return -1;
+  FinishTable tab = {};
+  for (int b = 0; b < B; ++b) {
+    tab.oh[b] = table[3 * b];
+    tab.ow[b] = table[3 * b + 1];
+    tab.scale[b] = table[3 * b + 2];
+  }
+  detections_finish_kernel<<<B, kBlock, 0, stream>>>(boxes, scores, labels, tab, D, thr, rows, count);
+  return hipGetLastError() == hipSuccess ? 0 : -3;
 }
