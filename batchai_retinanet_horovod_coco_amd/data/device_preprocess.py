@@ -11,6 +11,7 @@ bit-identical between the two paths.
 """
 from __future__ import annotations
 
+import threading
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -18,6 +19,25 @@ import torch
 
 from ..utils import cpu_native
 from .image import CAFFE_MEAN_BGR, compute_resize_scale
+
+
+# Training batches on a CUDA device: True builds the whole batch with one host->device copy and one launch of
+# batch_warp_resize_norm_kernel (bit-identical to the per-image route in caffe mode, tests/test_train_batch_gpu.py);
+# False keeps the per-image route (one copy, warp_norm_kernel and resize_kernel per image into a zero-filled batch).
+# Read at every batch by DevicePreprocessor.__call__ and ProcessEnqueuer._assemble, so scripts/bench_switch.py and
+# scripts/bench_train_batch.py can flip it inside one process.
+TRAIN_FUSED = True
+# one-launch route of DevicePreprocessor.__call__: start the host->device copy of the packed images every this many
+# bytes (an 800x1333 image is 3.2 MB), so a large batch's transfer overlaps the host packing the rest; a batch
+# smaller than this goes in one copy
+STAGE_CHUNK_BYTES = 4 << 20
+
+
+def transform_codes(params):
+    """(interp, border, cval) of the generator's ``TransformParameters`` as the kernels take them."""
+    if params is None:
+        return 1, 1, 0.0
+    return cpu_native.INTERP[params.interpolation], cpu_native.BORDER[params.fill_mode], float(params.cval)
 
 
 def normalization(mode: str = "caffe"):
@@ -39,6 +59,7 @@ class DevicePreprocessor:
         self.min_side, self.max_side = min_side, max_side
         self.scale, self.mean = normalization(mode)
         self.dtype = dtype
+        self._stage_lock = threading.Lock()     # loader threads build training batches concurrently
 
     def output_size(self, hw: Sequence[int]):
         s = compute_resize_scale(hw, min_side=self.min_side, max_side=self.max_side)
@@ -46,14 +67,33 @@ class DevicePreprocessor:
 
     def __call__(self, images: List[np.ndarray], matrices: List[Optional[np.ndarray]], batch_size: int,
                  params=None) -> torch.Tensor:
+        """The training batch of ``images`` (uint8 BGR HWC), image i warped by ``matrices[i]`` (``None``: no warp).
+        On a CUDA device with ``TRAIN_FUSED``: one staged copy and one launch (per 32 slots) that writes every value
+        of the batch; otherwise :meth:`per_image`."""
+        if not (TRAIN_FUSED and self.device.type == "cuda"):
+            return self.per_image(images, matrices, batch_size, params)
+        from ..ops import native
+        from .generator import pad_shape
+        sizes = [self.output_size(im.shape[:2])[0] for im in images]
+        Hm, Wm = pad_shape((max(s[0] for s in sizes), max(s[1] for s in sizes)), self.pad_multiple)
+        interp, border, cval = transform_codes(params)
+        staging, offsets = self._stage(images, chunk_bytes=STAGE_CHUNK_BYTES)
+        table = [(off, im.shape[0], im.shape[1], oh, ow) for off, im, (oh, ow) in zip(offsets, images, sizes)]
+        batch = torch.empty((batch_size, Hm, Wm, 3), dtype=self.dtype, device=self.device)
+        native.image_batch_warp_resize_normalize(staging, table, list(matrices), batch, len(images), interp, border,
+                                                 cval, self.scale, self.mean)
+        return batch
+
+    def per_image(self, images: List[np.ndarray], matrices: List[Optional[np.ndarray]], batch_size: int,
+                  params=None) -> torch.Tensor:
+        """The per-image route: one copy, warp_norm_kernel into an fp32 image at source size and resize_kernel into
+        the zero-filled batch, for each image."""
         from ..ops import native
         sizes = [self.output_size(im.shape[:2])[0] for im in images]
         from .generator import pad_shape
         Hm, Wm = pad_shape((max(s[0] for s in sizes), max(s[1] for s in sizes)), self.pad_multiple)
         batch = torch.zeros((batch_size, Hm, Wm, 3), dtype=self.dtype, device=self.device)
-        interp = cpu_native.INTERP[params.interpolation] if params is not None else 1
-        border = cpu_native.BORDER[params.fill_mode] if params is not None else 1
-        cval = float(params.cval) if params is not None else 0.0
+        interp, border, cval = transform_codes(params)
         for i, (im, M, (oh, ow)) in enumerate(zip(images, matrices, sizes)):
             host = torch.from_numpy(np.ascontiguousarray(im, dtype=np.uint8))
             if self.device.type == "cuda":
@@ -63,11 +103,18 @@ class DevicePreprocessor:
             native.image_resize_into(f, batch, i, (oh, ow))
         return batch
 
-    # ------------------------------------------------------------------ evaluation batches
-    def _stage(self, images: List[np.ndarray]):
+    # ------------------------------------------------------------------ staging (evaluation and one-launch training batches)
+    def _stage(self, images: List[np.ndarray], chunk_bytes: int = 0):
         """Pack the uint8 images into one of two pinned host buffers and start ONE async copy to the device.
         The buffers alternate; the event recorded after a buffer's copy is waited for before that buffer is
-        written again, so a copy that may still be in flight never reads a half-refilled buffer."""
+        written again, so a copy that may still be in flight never reads a half-refilled buffer.
+
+        ``chunk_bytes`` > 0 (training batches): the copy of what is packed so far is started whenever that many
+        bytes are waiting, so the transfer of a large batch runs while the host still packs the rest of it."""
+        with self._stage_lock:
+            return self._stage_locked(images, chunk_bytes)
+
+    def _stage_locked(self, images: List[np.ndarray], chunk_bytes: int = 0):
         st = getattr(self, "_staging", None)
         if st is None:
             st = self._staging = {"next": 0, "host": [None, None], "event": [None, None]}
@@ -84,17 +131,22 @@ class DevicePreprocessor:
         if host is None or host.numel() < total:
             host = st["host"][k] = torch.empty(max(total, 1), dtype=torch.uint8, pin_memory=cuda)
         view = host.numpy()
+        dev = torch.empty(max(total, 1), dtype=torch.uint8, device=self.device)
+        sent = 0
         for im, off in zip(images, offsets):
             n = im.shape[0] * im.shape[1] * 3
             view[off:off + n] = np.ascontiguousarray(im, dtype=np.uint8).reshape(-1)
-        dev = torch.empty(max(total, 1), dtype=torch.uint8, device=self.device)
-        dev[:total].copy_(host[:total], non_blocking=True)
+            if chunk_bytes > 0 and off + n - sent >= chunk_bytes and off + n < total:
+                dev[sent:off + n].copy_(host[sent:off + n], non_blocking=True)
+                sent = off + n
+        dev[sent:total].copy_(host[sent:total], non_blocking=True)
         if cuda:
             if st["event"][k] is None:
                 st["event"][k] = torch.cuda.Event()
             st["event"][k].record()
         return dev, offsets
 
+    # ------------------------------------------------------------------ evaluation batches
     def build_eval_batch(self, images: List[np.ndarray], batch_size: int):
         """The evaluation batch of ``images`` (uint8 BGR HWC), built by one kernel launch per 32 slots.
 

@@ -15,9 +15,10 @@ Here the host work moves into worker PROCESSES:
   writes the uint8 pixels into a slot of one shared-memory arena (``multiprocessing.shared_memory``), which
   the parent registers with the HIP runtime once (``hipHostRegister``: the host->device copy reads the
   arena directly, no staging copy);
-* a collector thread in the parent turns each finished slot into the padded device batch (the HIP
-  warp / normalise / resize kernels of ``DevicePreprocessor``) on a copy stream, waits for the copies, and
-  recycles the slot; batches come out in submission order.
+* a collector thread in the parent turns each finished slot into the padded device batch on a copy stream (one
+  copy of the slot's used range and one launch of the warp / normalise / resize / pad kernel of
+  ``csrc/kernels/image.hip``; ``device_preprocess.TRAIN_FUSED = False``: a copy and two kernels per image), waits
+  for the copies, and recycles the slot; batches come out in submission order.
 
 Workers are started from a ``forkserver`` started BEFORE the process touches the GPU (:func:`prestart`,
 called at the top of ``bin/train.py``): no worker is ever forked from, or exec'd by, a process that has
@@ -170,6 +171,36 @@ def _worker(gen, task_q, result_q, shm_name: str, nslots: int, slot_bytes: int) 
 
 
 # ------------------------------------------------------------------------------------------ parent side
+def plan_train_batch(metas):
+    """The one-copy, one-launch plan of a slot's ``metas`` (``(shape, off, M, out_hw, ann, inline)`` per image, as
+    the workers write them; ``off < 0``: the pixels are in ``inline``, not in the arena).
+
+    Returns ``(lo, span, total, table, matrices, inlines)``: the used byte range ``[lo, lo + span)`` of the arena
+    slot (smallest offset to largest ``off + n``; ``span`` 0 when every image is inline) is copied to the start of a
+    ``total``-byte device staging buffer and the inline images follow it, ``inlines[k] = (staging offset, metas
+    index)``.  ``table[i]`` is image i's ``(staging offset, H, W, OH, OW)`` and ``matrices[i]`` its matrix or
+    ``None``, in the order of ``metas``."""
+    sizes = [int(m[0][0]) * int(m[0][1]) * 3 for m in metas]
+    inside = [(m[1], n) for m, n in zip(metas, sizes) if m[1] >= 0]
+    lo = min((off for off, _ in inside), default=0)
+    span = max((off + n for off, n in inside), default=lo) - lo
+    total = span
+    table, matrices, inlines = [], [], []
+    for i, (m, n) in enumerate(zip(metas, sizes)):
+        shape, off, M, out_hw = m[0], m[1], m[2], m[3]
+        if len(shape) != 3 or shape[2] != 3:
+            raise ValueError("plan_train_batch wants HWC images with 3 channels, got {}".format(tuple(shape)))
+        if off >= 0:
+            at = off - lo
+        else:
+            at = total
+            inlines.append((at, i))
+            total += n
+        table.append((int(at), int(shape[0]), int(shape[1]), int(out_hw[0]), int(out_hw[1])))
+        matrices.append(M)
+    return int(lo), int(span), int(total), table, matrices, inlines
+
+
 class ProcessEnqueuer:
     """``GeneratorEnqueuer``-compatible (``start`` / ``get`` / ``stop``) loader with worker processes.
 
@@ -346,10 +377,9 @@ class ProcessEnqueuer:
         """Device batch from one slot (on the copy stream); the slot is recycled once its copies are done."""
         if self.device.type != "cuda":
             return self._assemble_host(slot, metas)
-        from ..ops import native
-        from ..utils import cpu_native
+        from . import device_preprocess
+        from .device_preprocess import transform_codes
         gen = self.gen
-        pre = gen.device_preprocessor
         B = gen.batch_size
         from .generator import pad_shape
         H0 = max(m[3][0] for m in metas)
@@ -357,27 +387,13 @@ class ProcessEnqueuer:
         # the batch canvas is the largest image rounded up to --pad-multiple (shape classes), exactly as the
         # thread path (Generator.compute_input_output) and DevicePreprocessor pad it
         Hm, Wm = pad_shape((H0, W0), getattr(gen, "pad_multiple", 0))
-        params = gen.transform_parameters
-        interp = cpu_native.INTERP[params.interpolation] if params is not None else 1
-        border = cpu_native.BORDER[params.fill_mode] if params is not None else 1
-        cval = float(params.cval) if params is not None else 0.0
+        interp, border, cval = transform_codes(gen.transform_parameters)
         ctx = torch.cuda.stream(self._stream) if self._stream is not None else _Null()
         with ctx:
-            batch = torch.zeros((B, Hm, Wm, 3), dtype=pre.dtype, device=self.device)
-            for i, (shape, off, M, out_hw, ann, inline) in enumerate(metas):
-                if off >= 0:
-                    n = int(np.prod(shape))
-                    host = self.arena[slot, off:off + n].view(*shape)
-                    if not self._registered and self.device.type == "cuda":
-                        host = host.pin_memory()
-                else:
-                    host = torch.from_numpy(inline)
-                    self.stats["inline_images"] += 1
-                    if self.device.type == "cuda":
-                        host = host.pin_memory()
-                src = host.to(self.device, non_blocking=True)
-                f = native.image_warp_normalize(src, M, None, interp, border, cval, pre.scale, pre.mean)
-                native.image_resize_into(f, batch, i, out_hw)
+            if device_preprocess.TRAIN_FUSED:
+                batch = self._fused_batch(slot, metas, (B, Hm, Wm, 3), interp, border, cval)
+            else:
+                batch = self._per_image_batch(slot, metas, (B, Hm, Wm, 3), interp, border, cval)
             ev = None
             if self._stream is not None:
                 ev = torch.cuda.Event()
@@ -401,6 +417,51 @@ class ProcessEnqueuer:
         out = {"images": batch, "gt": torch.from_numpy(gt), "gt_count": torch.from_numpy(cnt),
                "image_hw": torch.from_numpy(hw)}
         return out, ev
+
+    def _fused_batch(self, slot: int, metas, shape, interp, border, cval):
+        """One copy of the used range of the arena slot (plus one of the inline images, if any), one launch."""
+        from ..ops import native
+        pre = self.gen.device_preprocessor
+        lo, span, total, table, matrices, inlines = plan_train_batch(metas)
+        staging = torch.empty(max(total, 1), dtype=torch.uint8, device=self.device)
+        if span:
+            host = self.arena[slot, lo:lo + span]
+            if not self._registered:
+                host = host.pin_memory()
+            staging[:span].copy_(host, non_blocking=True)
+        if inlines:
+            self.stats["inline_images"] += len(inlines)
+            host = torch.empty(total - span, dtype=torch.uint8, pin_memory=True)
+            view = host.numpy()
+            for at, i in inlines:
+                px = np.ascontiguousarray(metas[i][5], dtype=np.uint8).reshape(-1)
+                view[at - span:at - span + px.size] = px
+            staging[span:total].copy_(host, non_blocking=True)
+        batch = torch.empty(shape, dtype=pre.dtype, device=self.device)
+        native.image_batch_warp_resize_normalize(staging, table, matrices, batch, len(metas), interp, border, cval,
+                                                 pre.scale, pre.mean)
+        return batch
+
+    def _per_image_batch(self, slot: int, metas, shape, interp, border, cval):
+        """The per-image route: a copy, warp_norm_kernel and resize_kernel per image into a zero-filled batch."""
+        from ..ops import native
+        pre = self.gen.device_preprocessor
+        batch = torch.zeros(shape, dtype=pre.dtype, device=self.device)
+        for i, (shp, off, M, out_hw, ann, inline) in enumerate(metas):
+            if off >= 0:
+                n = int(np.prod(shp))
+                host = self.arena[slot, off:off + n].view(*shp)
+                if not self._registered and self.device.type == "cuda":
+                    host = host.pin_memory()
+            else:
+                host = torch.from_numpy(inline)
+                self.stats["inline_images"] += 1
+                if self.device.type == "cuda":
+                    host = host.pin_memory()
+            src = host.to(self.device, non_blocking=True)
+            f = native.image_warp_normalize(src, M, None, interp, border, cval, pre.scale, pre.mean)
+            native.image_resize_into(f, batch, i, out_hw)
+        return batch
 
     def _assemble_host(self, slot: int, metas):
         """CPU device: the host pipeline's image work (normalise -> warp -> resize -> pad, the functions

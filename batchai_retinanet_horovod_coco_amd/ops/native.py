@@ -113,6 +113,8 @@ _SIGS = {
     "mxr_image_resize_into": [c_vp, c_int, c_int, c_vp, c_int, c_int, c_ll, c_int, c_vp],
     "mxr_image_batch_resize_normalize": [c_vp, c_ll, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_float, c_float,
                                          c_float, c_float, c_vp],
+    "mxr_image_batch_warp_resize_normalize": [c_vp, c_ll, c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_int,
+                                              c_int, c_float, c_float, c_float, c_float, c_float, c_vp],
     "mxr_detections_finish": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_float, c_vp, c_vp, c_vp],
     "mxr_fp8_amax": [c_vp, c_ll, c_vp, c_vp],
     "mxr_fp8_quant": [c_vp, c_ll, c_vp, c_vp, c_vp, c_vp],
@@ -1067,6 +1069,40 @@ def image_batch_resize_normalize(staging: torch.Tensor, table, batch: torch.Tens
         _chk(lib().mxr_image_batch_resize_normalize(_p(staging), int(staging.numel()), tab[b0:].ctypes.data, n,
                                                     _p(batch[b0:]), nb, Hm, Wm, dt, float(scale), float(mean[0]),
                                                     float(mean[1]), float(mean[2]), _s()), "image_batch")
+
+
+def image_batch_warp_resize_normalize(staging: torch.Tensor, table, matrices, batch: torch.Tensor, n_images: int,
+                                      interp: int = 1, border: int = 1, cval: float = 0.0, scale: float = 1.0,
+                                      mean=(0.0, 0.0, 0.0)) -> None:
+    """The training counterpart of :func:`image_batch_resize_normalize`: image i is additionally warped at its own
+    size by the forward 2x3 (or 3x3) affine ``matrices[i]`` (``cv2.warpAffine``; ``None``: no warp) between the
+    normalisation and the resize -- per value what :func:`image_warp_normalize` then :func:`image_resize_into`
+    give, without the fp32 intermediate.  ``interp`` / ``border`` / ``cval`` hold for the whole batch.  Every value
+    of ``batch`` is written; one launch per 32 slots (csrc/kernels/image.hip)."""
+    import numpy as np
+    assert staging.dtype == torch.uint8 and staging.is_contiguous() and staging.device == batch.device
+    assert batch.dim() == 4 and batch.shape[3] == 3 and batch.is_contiguous()
+    B, Hm, Wm = int(batch.shape[0]), int(batch.shape[1]), int(batch.shape[2])
+    n_images = int(n_images)
+    rows = np.asarray(table, dtype=np.int64).reshape(-1, 5)
+    if rows.shape[0] != n_images or n_images > B or len(matrices) != n_images:
+        raise ValueError("image_batch_warp_resize_normalize: {} table rows, {} matrices, {} images, {} slots".format(
+            rows.shape[0], len(matrices), n_images, B))
+    tab = np.zeros((n_images, 6), dtype=np.int64)
+    tab[:, :5] = rows
+    mats = np.zeros((max(n_images, 1), 6), dtype=np.float64)
+    for i, M in enumerate(matrices):
+        if M is not None:
+            tab[i, 5] = 1
+            mats[i] = np.asarray(M, dtype=np.float64).reshape(-1)[:6]
+    dt = _dt(batch)
+    for b0 in range(0, B, BATCH_SLOTS):
+        nb = min(BATCH_SLOTS, B - b0)
+        n = max(0, min(nb, n_images - b0))
+        _chk(lib().mxr_image_batch_warp_resize_normalize(
+            _p(staging), int(staging.numel()), tab[b0:].ctypes.data, mats[min(b0, mats.shape[0] - 1):].ctypes.data, n,
+            _p(batch[b0:]), nb, Hm, Wm, dt, int(interp), int(border), float(cval), float(scale), float(mean[0]),
+            float(mean[1]), float(mean[2]), _s()), "image_batch_warp")
 
 
 # =========================================================================================
