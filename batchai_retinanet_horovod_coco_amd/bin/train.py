@@ -8,7 +8,7 @@ Same subcommands, flags, defaults and argument checks as ``/root/reference/train
 ``--no-evaluation``, ``--freeze-backbone``, ``--random-transform``, ``--image-min-side``,
 ``--image-max-side``), plus a ``synthetic`` dataset and MI355X options (``--dtype``, ``--clip-mode``,
 ``--bucket-mb``, ``--allreduce-dtype``, ``--workers``, ``--shard-data``, ``--checkpoint-format``,
-``--lr``, ``--clipnorm``, ``--seed``, ``--log-every``, ``--no-metric-average``, ``--log-all-ranks``,
+``--lr``, ``--clipnorm``, ``--optimizer``, ``--momentum``, ``--nesterov``, ``--weight-decay``, ``--warmup-epochs``, ``--seed``, ``--log-every``, ``--no-metric-average``, ``--log-all-ranks``,
 ``--metrics-jsonl``, ``--stop-on-nan``, ``--graph``, ``--graph-shapes``, ``--eval-batch-size``,
 ``--eval-pad-multiple``, ``--eval-workers``).
 
@@ -54,9 +54,33 @@ def check_args(parsed_args):
                          "the host every step, which a replayed step would skip")
     if getattr(parsed_args, "graph_shapes", 1) < 1:
         raise SystemExit("--graph-shapes must be at least 1")
+    resolve_optimizer(parsed_args)
+    if getattr(parsed_args, "warmup_epochs", 0) < 0:
+        raise SystemExit("--warmup-epochs must be >= 0")
     if "resnet" not in parsed_args.backbone:
         warnings.warn("Using experimental backbone {}. Only resnet50 has been properly tested.".format(
             parsed_args.backbone))
+    return parsed_args
+
+
+def resolve_optimizer(parsed_args):
+    """``--optimizer`` when given, else the class stored in ``--snapshot``, else adam.  An explicit flag that
+    contradicts the snapshot, and ``--weight-decay`` with adam, are contradictions."""
+    if not hasattr(parsed_args, "optimizer"):
+        return parsed_args
+    stored = None
+    if parsed_args.snapshot and os.path.exists(parsed_args.snapshot):
+        from ..io import checkpoint
+        cls = checkpoint.stored_optimizer_class(parsed_args.snapshot)
+        stored = cls.lower() if cls else None
+    if parsed_args.optimizer is None:
+        parsed_args.optimizer = stored if stored in ("adam", "sgd") else "adam"
+    elif stored is not None and stored != parsed_args.optimizer:
+        raise SystemExit("--optimizer {} contradicts --snapshot {}, which was written by {}: drop the flag to resume "
+                         "with {}, or start from --weights".format(parsed_args.optimizer, parsed_args.snapshot, stored,
+                                                                  stored))
+    if parsed_args.weight_decay and parsed_args.optimizer == "adam":
+        raise SystemExit("--weight-decay goes with --optimizer sgd; weight decay for adam is not implemented")
     return parsed_args
 
 
@@ -152,7 +176,20 @@ def build_parser() -> argparse.ArgumentParser:
                              "prints one JSON line (images/sec for the whole job) instead of training epochs.")
     parser.add_argument("--allreduce-dtype", choices=["fp32", "bf16", "fp16"], default="fp32")
     parser.add_argument("--lr", type=float, default=1e-5)
-    parser.add_argument("--clipnorm", type=float, default=0.001)
+    parser.add_argument("--clipnorm", type=float, default=0.001,
+                        help="Clip the global gradient norm to this (default: the reference's Adam recipe; SGD runs "
+                             "will want their own value; 0 turns clipping off).")
+    parser.add_argument("--optimizer", choices=["adam", "sgd"], default=None,
+                        help="adam (default): the reference's Keras Adam.  sgd: Keras SGD with --momentum, --nesterov "
+                             "and --weight-decay in one fused kernel.  With --snapshot the class stored in the file "
+                             "is used unless this flag is given.")
+    parser.add_argument("--momentum", type=float, default=0.9, help="SGD momentum (used by --optimizer sgd).")
+    parser.add_argument("--nesterov", action="store_true", help="Nesterov momentum (--optimizer sgd).")
+    parser.add_argument("--weight-decay", type=float, default=0.0,
+                        help="Coupled L2 weight decay on the conv kernels, not on biases (--optimizer sgd only).")
+    parser.add_argument("--warmup-epochs", type=float, default=0, metavar="E",
+                        help="Horovod's gradual warmup over the first E epochs, from lr / ranks up to --lr "
+                             "(--lr is the rate after the warmup).  Default 0: off.")
     parser.add_argument("--workers", type=int, default=1, help="Data loading workers (Keras default 1).")
     parser.add_argument("--loader", choices=["auto", "thread", "process"], default="auto",
                         help="Worker kind: 'process' decodes in worker processes into a pinned shared-memory arena "
@@ -254,6 +291,9 @@ def create_callbacks(trainer, prediction_model, validation_generator, args):
     from ..eval.callbacks import CocoEval, Evaluate
     rank = runtime.rank()
     callbacks = [hvd_callbacks.BroadcastGlobalVariablesCallback(0)]
+    if getattr(args, "warmup_epochs", 0) > 0:
+        callbacks.append(hvd_callbacks.LearningRateWarmupCallback(warmup_epochs=args.warmup_epochs,
+                                                                  steps_per_epoch=args.steps))
     if args.metric_average and runtime.size() > 1:
         callbacks.append(hvd_callbacks.MetricAverageCallback())
     if rank == 0 and args.snapshots:
@@ -409,11 +449,11 @@ def main(args=None):
     comp = {"fp32": Compression.none, "bf16": Compression.bf16, "fp16": Compression.fp16}[args.allreduce_dtype]
     trainer = Trainer(model, lr=args.lr, clipnorm=args.clipnorm, compute_dtype=dtype, clip_mode=args.clip_mode,
                       compression=comp, bucket_bytes=int(args.bucket_mb * 2 ** 20) if args.bucket_mb else None,
-                      device=dev, overlap=not args.no_overlap)
+                      device=dev, overlap=not args.no_overlap,
+                      **(dict(optimizer="sgd", momentum=args.momentum, nesterov=args.nesterov,
+                              weight_decay=args.weight_decay) if args.optimizer == "sgd" else {}))
     if args.snapshot is not None:
-        checkpoint.load_optimizer_h5(model, trainer.base_optimizer, args.snapshot) \
-            if not args.snapshot.endswith(".safetensors") else \
-            checkpoint.load_safetensors(model, args.snapshot, trainer.base_optimizer)
+        checkpoint.load_optimizer(model, trainer.base_optimizer, args.snapshot)
         initial_epoch = checkpoint.checkpoint_epoch(args.snapshot) or 0
         trainer.on_weights_changed()
 

@@ -20,6 +20,7 @@ from __future__ import annotations
 import json
 import os
 import re
+import warnings
 from collections import OrderedDict
 from typing import Dict, List, Optional, Tuple
 
@@ -77,9 +78,46 @@ def model_config(model) -> Dict:
                        "layers": list(keras_layers(model).keys())}}
 
 
+def optimizer_class(optimizer) -> Optional[str]:
+    """The Keras class name of a live optimizer (a ``DistributedOptimizer`` answers for the one it wraps)."""
+    if optimizer is None:
+        return None
+    return getattr(getattr(optimizer, "optimizer", optimizer), "class_name", None) or "Adam"
+
+
+def _slots(optimizer) -> List[torch.Tensor]:
+    """The optimizer's per-parameter state buffers in the order Keras lists them (Adam: m, v; SGD: velocity)."""
+    st = optimizer.state_tensors()
+    return [st[k] for k in (("m", "v") if optimizer_class(optimizer) == "Adam" else ("velocity",))]
+
+
+def stored_optimizer_class(path: str) -> Optional[str]:
+    """The optimizer class a checkpoint was written with (None when it stores no training config)."""
+    if path.endswith(".safetensors"):
+        from safetensors import safe_open
+        with safe_open(path, framework="pt") as f:
+            meta = f.metadata() or {}
+        raw = meta.get("training_config")
+    else:
+        raw = hdf5.File(path, "r").attrs.get("training_config")
+        raw = bytes(raw).decode() if raw is not None else None
+    if not raw:
+        return None
+    return json.loads(raw).get("optimizer_config", {}).get("class_name")
+
+
+def _class_mismatch(path: str, optimizer) -> bool:
+    stored, live = stored_optimizer_class(path), optimizer_class(optimizer)
+    if stored is not None and stored != live:
+        warnings.warn("{} holds {} state, the live optimizer is {}: weights loaded, optimizer state left fresh"
+                      .format(path, stored, live))
+        return True
+    return False
+
+
 def training_config(optimizer) -> Dict:
     cfg = optimizer.get_config() if optimizer is not None else {}
-    return {"optimizer_config": {"class_name": "Adam", "config": cfg},
+    return {"optimizer_config": {"class_name": optimizer_class(optimizer) or "Adam", "config": cfg},
             "loss": {"regression": "_smooth_l1", "classification": "_focal"},
             "metrics": [], "sample_weight_mode": None, "loss_weights": None}
 
@@ -156,6 +194,17 @@ def save_keras_h5(path: str, model, optimizer=None, epoch: Optional[int] = None,
                 ow.create_dataset(name, data=np.zeros((1,), dtype=np.float32))
                 names.append(name)
             hdf5.save_attributes_to_hdf5_group(ow, "weight_names", [x.encode() for x in names])
+        elif include_optimizer and optimizer is not None and optimizer_class(optimizer) == "SGD":
+            ow = f.create_group("optimizer_weights")
+            names = ["SGD/iterations:0"]
+            ow.create_dataset(names[0], data=np.array(int(optimizer.iterations), dtype=np.int64))
+            flat, buf = optimizer.flat, _slots(optimizer)[0]
+            for i, (p, kind) in enumerate(_keras_order_params(model)):
+                name = "training/SGD/Variable{}:0".format("" if i == 0 else "_{}".format(i))
+                off, num = _flat_slice(flat, p)
+                ow.create_dataset(name, data=_to_keras(buf[off:off + num].detach().cpu().numpy().reshape(p.shape), kind))
+                names.append(name)
+            hdf5.save_attributes_to_hdf5_group(ow, "weight_names", [x.encode() for x in names])
     return path
 
 
@@ -210,21 +259,26 @@ def load_weights(model, path: str, by_name: bool = True, skip_mismatch: bool = F
 
 
 def load_optimizer_h5(model, optimizer, path: str) -> bool:
+    """Restore the optimizer state a Keras-layout file holds.  False (state untouched) when the file has none, or
+    holds another optimizer class's: slots are never matched by position across classes."""
     f = hdf5.File(path, "r")
     if "optimizer_weights" not in f:
+        return False
+    if _class_mismatch(path, optimizer):
         return False
     ow = f["optimizer_weights"]
     names = hdf5.load_attributes_from_hdf5_group(ow, "weight_names")
     params = _keras_order_params(model)
     n = len(params)
-    if len(names) < 1 + 2 * n:
+    slots = _slots(optimizer)
+    if len(names) < 1 + len(slots) * n or not names[0].startswith(optimizer_class(optimizer) + "/"):
         return False
     optimizer.iterations = int(np.asarray(ow[names[0]]).reshape(-1)[0])
     flat = optimizer.flat
     with torch.no_grad():
-        for slot, buf in (("m", optimizer.m), ("v", optimizer.v)):
+        for k, buf in enumerate(slots):
             for i, (p, kind) in enumerate(params):
-                idx = 1 + (i if slot == "m" else n + i)
+                idx = 1 + k * n + i
                 a = _from_keras(np.asarray(ow[names[idx]]), kind)
                 off, num = _flat_slice(flat, p)
                 buf[off:off + num].copy_(torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(buf.device))
@@ -284,6 +338,11 @@ def save_safetensors(path: str, model, optimizer=None, epoch: Optional[int] = No
         meta["iterations"] = str(int(optimizer.iterations))
         meta["lr"] = repr(float(optimizer.lr))
         meta["training_config"] = json.dumps(training_config(optimizer))
+    elif optimizer is not None and optimizer_class(optimizer) == "SGD":
+        tensors["__optimizer__.velocity"] = _slots(optimizer)[0].detach().cpu()
+        meta["iterations"] = str(int(optimizer.iterations))
+        meta["lr"] = repr(float(optimizer.lr))
+        meta["training_config"] = json.dumps(training_config(optimizer))
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tmp = path + ".tmp"
     save_file(tensors, tmp, metadata=meta)
@@ -292,6 +351,8 @@ def save_safetensors(path: str, model, optimizer=None, epoch: Optional[int] = No
 
 
 def load_safetensors(model, path: str, optimizer=None, skip_mismatch: bool = False):
+    """Returns (metadata, skipped tensors); ``metadata["optimizer_restored"]`` tells whether the optimizer state was
+    restored (only from a file written with the live optimizer's class)."""
     from safetensors.torch import load_file
     from safetensors import safe_open
     sd = load_file(path)
@@ -307,12 +368,18 @@ def load_safetensors(model, path: str, optimizer=None, skip_mismatch: bool = Fal
                     continue
                 raise ValueError("missing or mismatched tensor {}".format(k))
             v.copy_(sd[k].to(v.device, v.dtype))
-        if optimizer is not None and "__optimizer__.m" in sd and sd["__optimizer__.m"].numel() == optimizer.m.numel():
-            optimizer.m.copy_(sd["__optimizer__.m"].to(optimizer.m.device))
-            optimizer.v.copy_(sd["__optimizer__.v"].to(optimizer.v.device))
-            optimizer.iterations = int(meta.get("iterations", 0))
-            if "lr" in meta:
-                optimizer.lr = float(meta["lr"])
+        restored = False
+        if optimizer is not None and not _class_mismatch(path, optimizer):
+            state = optimizer.state_tensors()
+            keys = ["__optimizer__." + k for k in state]
+            if all(k in sd and sd[k].numel() == t.numel() for k, t in zip(keys, state.values())):
+                for k, t in zip(keys, state.values()):
+                    t.copy_(sd[k].to(t.device))
+                optimizer.iterations = int(meta.get("iterations", 0))
+                if "lr" in meta:
+                    optimizer.lr = float(meta["lr"])
+                restored = True
+    meta = dict(meta, optimizer_restored=restored)
     return meta, skipped
 
 
@@ -320,6 +387,14 @@ def save_checkpoint(path: str, model, optimizer=None, epoch: Optional[int] = Non
     if fmt == "safetensors" or path.endswith(".safetensors"):
         return save_safetensors(path, model, optimizer, epoch)
     return save_keras_h5(path, model, optimizer, epoch)
+
+
+def load_optimizer(model, optimizer, path: str) -> bool:
+    """Optimizer state from a checkpoint of either format; False when the file holds none for this optimizer class
+    (a safetensors file's weights are read again on the way)."""
+    if path.endswith(".safetensors"):
+        return bool(load_safetensors(model, path, optimizer)[0]["optimizer_restored"])
+    return load_optimizer_h5(model, optimizer, path)
 
 
 def restore_checkpoint(path: str, model, optimizer=None) -> Optional[int]:

@@ -51,6 +51,7 @@ _SIGS = {
     "mxr_chunk_struct_sizes": [c_vp],
     "mxr_adam_step": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_float, c_float,
                       c_float, c_vp],
+    "mxr_sgd_step": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp],
     "mxr_refresh_copy": [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp],
     "mxr_grad_norm_clip": [c_vp, c_ll, c_vp, c_float, c_float, c_float, c_vp, c_vp],
     "mxr_scale_inplace": [c_vp, c_ll, c_vp, c_vp],
@@ -427,12 +428,19 @@ class AdamPlan:
         self.iter = torch.zeros(1, dtype=torch.int64, device=dev)
         self.generation = 0
         self._lr = None
+        self._momentum = None
         self.host_iter = 0
 
     def set_lr(self, lr: float) -> None:
         if self._lr != lr:
             self.hyper[1] = lr
             self._lr = lr
+
+    def set_momentum(self, momentum: float) -> None:
+        """hyper[2], read by the fused SGD kernel (the Adam kernel takes its betas by value)."""
+        if self._momentum != momentum:
+            self.hyper[2] = momentum
+            self._momentum = momentum
 
     def sync_iter(self, iteration: int) -> None:
         """Make the device step counter hold ``iteration`` (a fill only when the host mirror disagrees)."""
@@ -732,6 +740,26 @@ def adam_step(flat, m, v, grad_scale, lr, iteration, b1, b2, eps, plan: Optional
     _chk(lib().mxr_adam_step(_p(flat.data), _p(flat.grad), _p(m), _p(v), _p(plan.copy), _p(plan.scales),
                              _p(plan.chunks), plan.nchunks, _p(plan.segs), _p(gs), _p(plan.hyper), _p(plan.iter),
                              b1, b2, eps, _s()), "adam")
+    plan.generation += 1     # the compute copies changed (ComputeWeights.flipped re-flips lazily)
+
+
+def sgd_step(flat, v, grad_scale, lr, momentum, iteration, nesterov, seg_wd, plan: Optional[AdamPlan] = None):
+    """Fused Keras-SGD (momentum, nesterov, coupled weight decay) on the flat buffers, over the flat buffer's
+    :class:`AdamPlan` tables.  ``lr`` is the learning rate of this step (``decay`` applied); it and ``momentum`` are
+    read from device memory.  ``seg_wd``: one fp32 decay factor per segment on the device, or None for no decay."""
+    plan = plan or adam_plan(flat)
+    plan.set_lr(lr)
+    plan.set_momentum(momentum)
+    plan.sync_iter(iteration)
+    plan.host_iter = iteration + 1
+    if seg_wd is not None and (seg_wd.numel() != len(flat.segments) or seg_wd.dtype != torch.float32
+                               or seg_wd.device != flat.data.device):
+        raise ValueError("sgd_step: seg_wd must hold one fp32 value per segment on the parameters' device")
+    gs = grad_scale.reshape(1).float().contiguous() if torch.is_tensor(grad_scale) else \
+        torch.full((1,), float(grad_scale), device=flat.data.device)
+    _chk(lib().mxr_sgd_step(_p(flat.data), _p(flat.grad), _p(v), _p(plan.copy), _p(plan.scales), _p(plan.chunks),
+                            plan.nchunks, _p(plan.segs), _p(seg_wd), _p(gs), _p(plan.hyper), _p(plan.iter),
+                            1 if nesterov else 0, _s()), "sgd")
     plan.generation += 1     # the compute copies changed (ComputeWeights.flipped re-flips lazily)
 
 

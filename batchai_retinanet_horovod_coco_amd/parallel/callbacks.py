@@ -51,12 +51,36 @@ class MetricAverageCallback(Callback):
             logs[k] = v
 
 
-class LearningRateWarmupCallback(Callback):
+class _MomentumCorrection(Callback):
+    """Horovod's ``momentum_correction``: the Keras form of the SGD velocity carries the learning rate
+    (``v = momentum * v - lr * g``), so the step that follows a change of ``lr`` runs with
+    ``momentum * new_lr / old_lr`` (Goyal et al. 2017, section 2.1) and the momentum is put back at that batch's end.
+    A model without a ``momentum`` attribute (Adam) is left alone."""
+
+    momentum_correction = True
+
+    def _set_lr(self, new_lr: float) -> None:
+        old_lr = float(self.model.lr)
+        self.model.lr = new_lr
+        if not self.momentum_correction or new_lr == old_lr or old_lr == 0 or not hasattr(self.model, "momentum"):
+            return
+        if getattr(self, "_restore_momentum", None) is None:
+            self._restore_momentum = float(self.model.momentum)
+        self.model.momentum = float(self.model.momentum) * new_lr / old_lr
+
+    def on_batch_end(self, batch, logs=None):
+        if getattr(self, "_restore_momentum", None) is not None:
+            self.model.momentum = self._restore_momentum
+            self._restore_momentum = None
+
+
+class LearningRateWarmupCallback(_MomentumCorrection):
     """Horovod-style gradual warmup: lr ramps from ``lr/size`` to ``lr`` over ``warmup_epochs``."""
 
     def __init__(self, warmup_epochs: float = 5, steps_per_epoch: Optional[int] = None, verbose: int = 0,
-                 initial_lr: Optional[float] = None):
+                 initial_lr: Optional[float] = None, momentum_correction: bool = True):
         super().__init__()
+        self.momentum_correction = momentum_correction
         self.warmup_epochs = warmup_epochs
         self.steps_per_epoch = steps_per_epoch
         self.verbose = verbose
@@ -78,7 +102,7 @@ class LearningRateWarmupCallback(Callback):
             return
         size = runtime.size() if runtime.is_initialized() else 1
         mult = 1.0 / size * (e * (size - 1) / self.warmup_epochs + 1)
-        self.model.lr = self.initial_lr * mult
+        self._set_lr(self.initial_lr * mult)
 
     def on_epoch_end(self, epoch, logs=None):
         if epoch + 1 == int(self.warmup_epochs):
@@ -87,12 +111,13 @@ class LearningRateWarmupCallback(Callback):
                 print("\nEpoch %d: finished gradual learning rate warmup to %g." % (epoch + 1, self.initial_lr))
 
 
-class LearningRateScheduleCallback(Callback):
+class LearningRateScheduleCallback(_MomentumCorrection):
     """lr = initial_lr * multiplier(epoch) for start_epoch <= epoch < end_epoch."""
 
     def __init__(self, multiplier, start_epoch: int = 0, end_epoch: Optional[int] = None,
-                 initial_lr: Optional[float] = None):
+                 initial_lr: Optional[float] = None, momentum_correction: bool = True):
         super().__init__()
+        self.momentum_correction = momentum_correction
         self.multiplier = multiplier if callable(multiplier) else (lambda e, m=multiplier: m)
         self.start_epoch = start_epoch
         self.end_epoch = end_epoch
@@ -104,4 +129,4 @@ class LearningRateScheduleCallback(Callback):
 
     def on_epoch_begin(self, epoch, logs=None):
         if epoch >= self.start_epoch and (self.end_epoch is None or epoch < self.end_epoch):
-            self.model.lr = self.initial_lr * self.multiplier(epoch)
+            self._set_lr(self.initial_lr * self.multiplier(epoch))

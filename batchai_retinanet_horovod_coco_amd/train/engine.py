@@ -23,7 +23,7 @@ from ..ops import losses
 from ..parallel import runtime
 from ..parallel.distributed_optimizer import DistributedOptimizer
 from .flat import FlatParams, backward_order
-from .optimizer import KerasAdam
+from .optimizer import KerasAdam, KerasSGD
 
 
 _ROCTX = os.environ.get("MXR_ROCTX", "0") == "1"
@@ -51,13 +51,22 @@ _PAD_FOCAL = os.environ.get("MXR_PAD_FOCAL", "1") == "1"
 class Trainer:
     def __init__(self, model, lr: float = 1e-5, clipnorm: float = 0.001, compute_dtype: torch.dtype = torch.float32,
                  clip_mode: str = "local", compression=None, bucket_bytes: Optional[int] = None,
-                 device: Optional[torch.device] = None, overlap: bool = True, target_backend: str = "auto"):
+                 device: Optional[torch.device] = None, overlap: bool = True, target_backend: str = "auto",
+                 optimizer: str = "adam", momentum: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0):
         from ..parallel.collectives import Compression
         self.device = device or (runtime.device() if runtime.is_initialized() else torch.device("cpu"))
         self.model = model.to(self.device)
         self.compute_dtype = compute_dtype
         self.flat = FlatParams(backward_order(self.model), device=self.device)
-        self.base_optimizer = KerasAdam(self.flat, lr=lr, clipnorm=clipnorm)
+        if optimizer == "adam":
+            if momentum or nesterov or weight_decay:
+                raise ValueError("momentum, nesterov and weight_decay belong to optimizer='sgd'")
+            self.base_optimizer = KerasAdam(self.flat, lr=lr, clipnorm=clipnorm)
+        elif optimizer == "sgd":
+            self.base_optimizer = KerasSGD(self.flat, lr=lr, momentum=momentum, nesterov=nesterov,
+                                           weight_decay=weight_decay, clipnorm=clipnorm)
+        else:
+            raise ValueError("optimizer must be 'adam' or 'sgd', got {!r}".format(optimizer))
         self.optimizer = DistributedOptimizer(self.base_optimizer, compression=compression or Compression.none,
                                               clip_mode=clip_mode, bucket_bytes=bucket_bytes, overlap=overlap)
         self.anchors = anchor_ops.AnchorCache()
@@ -255,6 +264,8 @@ class Trainer:
             for k, v in (("images", images), ("gt", gt), ("gt_count", gt_count), ("image_hw", image_hw)):
                 if v.data_ptr() != static[k].data_ptr():
                     static[k].copy_(v, non_blocking=True)
+            if plan is not None and hasattr(self.base_optimizer, "momentum"):
+                plan.set_momentum(self.base_optimizer.momentum)     # outside the graph, like the lr in enable_graphs
             graph.replay()
             # the captured Adam advances the device step counter; keep the host mirrors in sync
             self.base_optimizer.iterations += 1
@@ -288,7 +299,8 @@ class Trainer:
         return self.step_graphs
 
     def adam_plan(self):
-        """The fused Adam kernel's device tables and host mirrors (None where the torch expression runs)."""
+        """The fused optimizer kernel's device tables and host mirrors -- Adam and SGD share them -- (None where the
+        torch expression runs)."""
         from ..ops import native
         return native.adam_plan(self.flat) if self.base_optimizer._use_hip() else None
 
@@ -307,6 +319,17 @@ class Trainer:
     @lr.setter
     def lr(self, v: float) -> None:
         self.base_optimizer.lr = float(v)
+
+    @property
+    def momentum(self) -> float:
+        """The base optimizer's momentum (SGD); an AttributeError with Adam, which has none."""
+        return self.base_optimizer.momentum
+
+    @momentum.setter
+    def momentum(self, v: float) -> None:
+        if not hasattr(self.base_optimizer, "momentum"):
+            raise AttributeError("the {} optimizer has no momentum".format(self.base_optimizer.class_name))
+        self.base_optimizer.momentum = float(v)
 
     def state_for_broadcast(self):
         return [self.flat.data] + [b for b in self.model.buffers()]

@@ -1,4 +1,4 @@
-"""Keras-semantics Adam with ``clipnorm`` over flat fp32 buffers.
+"""Keras-semantics Adam and SGD with ``clipnorm`` over flat fp32 buffers.
 
 Spec: ``keras.optimizers.adam(lr=1e-5, clipnorm=0.001)`` at ``/root/reference/train.py:104``
 (SURVEY §2.8.7):
@@ -14,6 +14,10 @@ The update runs as ONE fused multi-tensor HIP kernel over the flat buffers on th
 (``csrc/kernels/optim.hip``: gradient pre-scale (1/world, clip factor) + Adam + refresh of
 the bf16 compute weights), and as the equivalent torch expression on the CPU.  The clip
 factor and lr_t live on the device so a step never synchronises with the host.
+
+:class:`KerasSGD` (Keras 2 ``SGD(lr, momentum, decay, nesterov)`` plus coupled weight decay) shares the norm, the
+clip factor and the backend choice with it (:class:`_FlatOptimizer`) and runs as one fused launch too
+(``mxr_sgd_step``).
 """
 from __future__ import annotations
 
@@ -25,31 +29,23 @@ import torch
 from .flat import FlatParams
 
 
-class KerasAdam:
-    def __init__(self, flat: FlatParams, lr: float = 1e-5, beta_1: float = 0.9, beta_2: float = 0.999,
-                 epsilon: float = 1e-7, decay: float = 0.0, clipnorm: Optional[float] = 0.001,
-                 amsgrad: bool = False, backend: str = "auto"):
-        if amsgrad:
-            raise NotImplementedError("amsgrad is off in the reference optimizer")
+class _FlatOptimizer:
+    """What every optimizer over the flat buffers shares: the global gradient norm, the ``clipnorm`` factor, the
+    choice between the fused HIP kernels and the torch expression, and Keras' ``decay`` schedule.  A subclass sets
+    ``class_name`` (the Keras class the checkpoints record) and implements ``apply`` / ``state_tensors`` /
+    ``get_config``."""
+
+    class_name = ""
+
+    def __init__(self, flat: FlatParams, lr: float, decay: float, clipnorm: Optional[float], backend: str):
         self.flat = flat
         self.lr = float(lr)
         self.initial_lr = float(lr)
-        self.beta_1, self.beta_2, self.epsilon, self.decay = beta_1, beta_2, epsilon, decay
+        self.decay = decay
         self.clipnorm = clipnorm
-        dev = flat.data.device
-        self.m = torch.zeros_like(flat.data)
-        self.v = torch.zeros_like(flat.data)
         self.iterations = 0                       # host mirror (the step count is deterministic)
         self.backend = backend
-        self._dev = dev
-
-    # -------------------------------------------------------------- keras-ish API
-    def get_config(self) -> Dict:
-        return {"lr": self.lr, "beta_1": self.beta_1, "beta_2": self.beta_2, "decay": self.decay,
-                "epsilon": self.epsilon, "amsgrad": False, "clipnorm": self.clipnorm}
-
-    def state_tensors(self):
-        return {"m": self.m, "v": self.v}
+        self._dev = flat.data.device
 
     def _use_hip(self) -> bool:
         from ..ops import native
@@ -82,12 +78,43 @@ class KerasAdam:
         return torch.where(norm >= c, c / norm.clamp_min(1e-30), torch.ones_like(norm))
 
     def base_lr(self, t: int) -> float:
-        """The learning rate of iteration ``t`` (1-based) before the bias correction, ``decay`` included: what the
+        """The learning rate of iteration ``t`` (1-based) before any bias correction, ``decay`` included: what the
         fused kernel is handed, by the eager step and -- outside the graph -- before every graph replay."""
         lr = self.lr
         if self.decay > 0:
             lr = lr * (1.0 / (1.0 + self.decay * (t - 1)))
         return lr
+
+    def step(self, world_size: int = 1) -> torch.Tensor:
+        """Local step (no communication): clip, then the update.  Returns the pre-clip norm."""
+        norm, scale = self.norm_and_scale(1.0, 1.0 / world_size)
+        self.apply(scale)
+        return norm
+
+    def zero_grad(self) -> None:
+        self.flat.zero_grad()
+
+
+class KerasAdam(_FlatOptimizer):
+    class_name = "Adam"
+
+    def __init__(self, flat: FlatParams, lr: float = 1e-5, beta_1: float = 0.9, beta_2: float = 0.999,
+                 epsilon: float = 1e-7, decay: float = 0.0, clipnorm: Optional[float] = 0.001,
+                 amsgrad: bool = False, backend: str = "auto"):
+        if amsgrad:
+            raise NotImplementedError("amsgrad is off in the reference optimizer")
+        super().__init__(flat, lr, decay, clipnorm, backend)
+        self.beta_1, self.beta_2, self.epsilon = beta_1, beta_2, epsilon
+        self.m = torch.zeros_like(flat.data)
+        self.v = torch.zeros_like(flat.data)
+
+    # -------------------------------------------------------------- keras-ish API
+    def get_config(self) -> Dict:
+        return {"lr": self.lr, "beta_1": self.beta_1, "beta_2": self.beta_2, "decay": self.decay,
+                "epsilon": self.epsilon, "amsgrad": False, "clipnorm": self.clipnorm}
+
+    def state_tensors(self):
+        return {"m": self.m, "v": self.v}
 
     def lr_t(self, t: int) -> float:
         lr = self.base_lr(t)
@@ -108,11 +135,79 @@ class KerasAdam:
             self.flat.data.addcdiv_(self.m, self.v.sqrt().add_(self.epsilon), value=-lr_t)
         self.iterations = t
 
-    def step(self, world_size: int = 1) -> torch.Tensor:
-        """Local step (no communication): clip, then Adam.  Returns the pre-clip norm."""
-        norm, scale = self.norm_and_scale(1.0, 1.0 / world_size)
-        self.apply(scale)
-        return norm
 
-    def zero_grad(self) -> None:
-        self.flat.zero_grad()
+class KerasSGD(_FlatOptimizer):
+    """Keras 2 ``SGD(lr, momentum, decay, nesterov)`` plus coupled L2 weight decay on the parameters of rank >= 2
+    (conv kernels; biases and every rank-1 parameter get none):
+
+        lr_t  = lr / (1 + decay * (t - 1))
+        g_eff = grad * grad_scale + wd_seg * p
+        v     = momentum * v - lr_t * g_eff
+        p     = p + v                        (nesterov: p + momentum * v - lr_t * g_eff)
+
+    The clip norm is taken over the raw gradients.  One fused HIP launch over the flat buffers on the GPU
+    (``mxr_sgd_step``), which also refreshes the bf16 compute copies; the torch expression elsewhere."""
+
+    class_name = "SGD"
+
+    def __init__(self, flat: FlatParams, lr: float = 0.01, momentum: float = 0.0, decay: float = 0.0,
+                 nesterov: bool = False, weight_decay: float = 0.0, clipnorm: Optional[float] = None,
+                 backend: str = "auto"):
+        if momentum < 0 or weight_decay < 0:
+            raise ValueError("momentum and weight_decay must be >= 0")
+        super().__init__(flat, lr, decay, clipnorm, backend)
+        self.momentum = float(momentum)
+        self.nesterov = bool(nesterov)
+        self.weight_decay = float(weight_decay)
+        self.velocity = torch.zeros_like(flat.data)
+        self._seg_wd = None         # (weight_decay it was built for, per-segment device table)
+        self._wd_flat = None        # the same per element, for the torch expression
+        if flat.data.is_cuda:
+            self.seg_wd()           # built now: a captured step must not meet its first upload
+
+    def get_config(self) -> Dict:
+        return {"lr": self.lr, "momentum": self.momentum, "decay": self.decay, "nesterov": self.nesterov,
+                "clipnorm": self.clipnorm, "weight_decay": self.weight_decay}
+
+    def state_tensors(self):
+        return {"velocity": self.velocity}
+
+    def segment_decay(self):
+        """``weight_decay`` for the segments of rank >= 2, 0 for the others: one value per segment."""
+        return [self.weight_decay if len(s.shape) >= 2 else 0.0 for s in self.flat.segments]
+
+    def seg_wd(self) -> Optional[torch.Tensor]:
+        """The kernel's per-segment decay table (persistent: a captured step holds its pointer), None without decay."""
+        if self.weight_decay == 0.0:
+            return None
+        if self._seg_wd is None or self._seg_wd[0] != self.weight_decay:
+            self._seg_wd = (self.weight_decay,
+                            torch.tensor(self.segment_decay(), dtype=torch.float32, device=self.flat.data.device))
+        return self._seg_wd[1]
+
+    def _decay_per_element(self) -> torch.Tensor:
+        if self._wd_flat is None or self._wd_flat[0] != self.weight_decay:
+            w = torch.zeros_like(self.flat.data)
+            for s, d in zip(self.flat.segments, self.segment_decay()):
+                w[s.offset:s.offset + s.numel] = d
+            self._wd_flat = (self.weight_decay, w)
+        return self._wd_flat[1]
+
+    def apply(self, grad_scale: torch.Tensor) -> None:
+        """SGD step with ``g_eff = grad * grad_scale + wd * p`` (grad_scale: 0-d device tensor)."""
+        t = self.iterations + 1
+        lr_t = self.base_lr(t)
+        if self._use_hip():
+            from ..ops import native
+            native.sgd_step(self.flat, self.velocity, grad_scale, lr_t, self.momentum, self.iterations, self.nesterov,
+                            self.seg_wd())
+        else:
+            g = self.flat.grad * grad_scale
+            if self.weight_decay != 0.0:
+                g = g + self._decay_per_element() * self.flat.data
+            self.velocity.mul_(self.momentum).add_(g, alpha=-lr_t)
+            if self.nesterov:
+                self.flat.data.add_(self.velocity, alpha=self.momentum).add_(g, alpha=-lr_t)
+            else:
+                self.flat.data.add_(self.velocity)
+        self.iterations = t

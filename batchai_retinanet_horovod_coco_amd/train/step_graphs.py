@@ -19,7 +19,8 @@ captured step per shape class and stays bit-identical to the eager run:
   before a capture (the lazily rebuilt data-gradient weight copies are rebuilt INSIDE the graph), one per replay
   (an eager step after a replay rebuilds them too).
 * **learning rate**: written before every replay through ``AdamPlan.set_lr`` (outside the graph), from the same
-  expression the eager ``KerasAdam.apply`` uses (``KerasAdam.base_lr``).
+  expression the eager ``KerasAdam.apply`` uses (``KerasAdam.base_lr``).  ``KerasSGD``'s momentum goes the same way
+  (``AdamPlan.set_momentum``).
 * **lifetime**: the persistent zero-padded gradient rows a captured step writes (``ops.native.ShapeSlots``) are
   pinned while its graph lives; ``Trainer.on_weights_changed`` drops every graph and the classes start over.
 * **failure**: a capture that raises, or one in which the conv tuner met a key it still has to race, is thrown
@@ -203,6 +204,8 @@ class StepGraphs:
             # the lr are brought up to date eagerly, so the captured pass finds them current
             plan.sync_iter(it0)
             plan.set_lr(opt.base_lr(it0 + 1))
+            if hasattr(opt, "momentum"):
+                plan.set_momentum(opt.momentum)
             plan.generation += 1        # the lazily rebuilt weight copies are rebuilt inside the graph
         misses0 = be.tuner_misses()
         reason = None
@@ -241,6 +244,8 @@ class StepGraphs:
         if plan is not None:
             plan.sync_iter(opt.iterations)
             plan.set_lr(opt.base_lr(opt.iterations + 1))
+            if hasattr(opt, "momentum"):
+                plan.set_momentum(opt.momentum)     # SGD: hyper[2], read by the replayed kernel
         logs = be.replay(e.graph, e.logs)
         # the captured Adam advanced the device step counter and rewrote the compute weights
         opt.iterations += 1

@@ -6,6 +6,11 @@
 // optimizer is graph-capturable and never syncs with the host:
 //   hyper[0] = lr_t (written by the prologue), hyper[1] = lr, iteration counter int64.
 // The same pass refreshes the bf16 "compute" weights (W * frozen-BN scale) the forward reads.
+//
+// Keras-SGD (momentum, nesterov, coupled L2 weight decay) runs over the same tables in one launch:
+//   g_eff = g * grad_scale + wd[seg] * p ;  v = momentum * v - lr * g_eff ;
+//   p += v   (nesterov: p += momentum * v - lr * g_eff)
+// with lr = hyper[1] and momentum = hyper[2] read from device memory (a replayed graph sees a changed value).
 #include "common.h"
 
 namespace {
@@ -90,6 +95,69 @@ __global__ __launch_bounds__(kBlock) void adam_kernel(float* __restrict__ p, con
   }
 }
 
+// One element of the SGD update; returns the new parameter, updates the velocity in place.
+template <bool NESTEROV, bool DECAY>
+__device__ __forceinline__ float sgd_elem(float p, float g, float& v, float gs, float wd, float lr, float mom) {
+  float ge = g * gs;
+  if (DECAY) ge += wd * p;
+  v = mom * v - lr * ge;
+  return NESTEROV ? p + mom * v - lr * ge : p + v;
+}
+
+template <bool NESTEROV, bool DECAY>
+__global__ __launch_bounds__(kBlock) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                     float* __restrict__ v, bf16_t* __restrict__ wcopy,
+                                                     const float* __restrict__ scales, const Chunk* __restrict__ chunks,
+                                                     const Seg* __restrict__ segs, const float* __restrict__ seg_wd,
+                                                     const float* __restrict__ grad_scale,
+                                                     const float* __restrict__ hyper, long long* __restrict__ iter) {
+  const Chunk c = chunks[blockIdx.x];
+  const Seg s = segs[c.seg];
+  const float gs = *grad_scale;
+  const float lr = hyper[1];
+  const float mom = hyper[2];
+  const float wd = DECAY ? seg_wd[c.seg] : 0.f;
+  // the step counter: nothing in this launch reads it
+  if (blockIdx.x == 0 && threadIdx.x == 0) *iter = *iter + 1;
+  const long long base = c.start;
+  const int nv = c.len >> 2;
+  for (int i = threadIdx.x; i < nv; i += kBlock) {
+    const long long e = base + 4LL * i;
+    float4 pp = *reinterpret_cast<const float4*>(p + e);
+    const float4 gg = *reinterpret_cast<const float4*>(g + e);
+    float4 vv = *reinterpret_cast<const float4*>(v + e);
+    float* pa = &pp.x; const float* ga = &gg.x; float* va = &vv.x;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pa[j] = sgd_elem<NESTEROV, DECAY>(pa[j], ga[j], va[j], gs, wd, lr, mom);
+    *reinterpret_cast<float4*>(p + e) = pp;
+    *reinterpret_cast<float4*>(v + e) = vv;
+    if (s.has_copy) {
+      const long long le = e - s.offset;
+      ushort4 w;
+      unsigned short* wa = &w.x;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float sc = 1.f;
+        if (s.scale_off >= 0) sc = scales[s.scale_off + (le + j) / s.row_len];
+        wa[j] = f2bf(pa[j] * sc);
+      }
+      *reinterpret_cast<ushort4*>(wcopy + e) = w;
+    }
+  }
+  // scalar tail (segment lengths that are not multiples of 4)
+  for (int i = (nv << 2) + threadIdx.x; i < c.len; i += kBlock) {
+    const long long e = base + i;
+    float vj = v[e];
+    const float pj = sgd_elem<NESTEROV, DECAY>(p[e], g[e], vj, gs, wd, lr, mom);
+    v[e] = vj; p[e] = pj;
+    if (s.has_copy) {
+      float sc = 1.f;
+      if (s.scale_off >= 0) sc = scales[s.scale_off + (e - s.offset) / s.row_len];
+      wcopy[e] = f2bf(pj * sc);
+    }
+  }
+}
+
 // Refresh only the bf16 compute copy (after loading weights / broadcast).
 __global__ __launch_bounds__(kBlock) void copy_kernel(const float* __restrict__ p, bf16_t* __restrict__ wcopy,
                                                       const float* __restrict__ scales, const Chunk* __restrict__ chunks,
@@ -165,6 +233,23 @@ MXR_API int mxr_adam_step(float* p, const float* g, float* m, float* v, void* wc
   adam_prologue<<<1, 1, 0, stream>>>(hyper, iter, b1, b2);
   adam_kernel<<<nchunks, kBlock, 0, stream>>>(p, g, m, v, (bf16_t*)wcopy, scales, (const Chunk*)chunks,
                                               (const Seg*)segs, grad_scale, hyper, b1, b2, eps);
+  return (int)hipGetLastError();
+}
+
+// seg_wd: one weight-decay factor per segment, or null (no decay anywhere: the form without the multiply).
+MXR_API int mxr_sgd_step(float* p, const float* g, float* v, void* wcopy, const float* scales, const void* chunks,
+                         int nchunks, const void* segs, const float* seg_wd, const float* grad_scale,
+                         const float* hyper, long long* iter, int nesterov, hipStream_t stream) {
+#define MXR_SGD(N, D)                                                                                         \
+  sgd_kernel<N, D><<<nchunks, kBlock, 0, stream>>>(p, g, v, (bf16_t*)wcopy, scales, (const Chunk*)chunks,     \
+                                                   (const Seg*)segs, seg_wd, grad_scale, hyper, iter)
+  if (nchunks <= 0) return (int)hipErrorInvalidValue;
+  if (nesterov) {
+    if (seg_wd) MXR_SGD(true, true); else MXR_SGD(true, false);
+  } else {
+    if (seg_wd) MXR_SGD(false, true); else MXR_SGD(false, false);
+  }
+#undef MXR_SGD
   return (int)hipGetLastError();
 }
 

@@ -1,0 +1,87 @@
+"""Fused optimizer steps on ResNet-50 RetinaNet's flat buffers (the real model, bf16 compute copies on), Adam and
+the SGD forms alternating in one process:  python scripts/bench_optim.py [--reps 15] [--calls 20]
+Each repetition times ``calls`` back-to-back steps of every form with device events; prints microseconds per step
+(median and the spread over the repetitions) and the HBM rate of the bytes the form moves per element
+(Adam: p, g, m, v read, p, m, v and the bf16 copy written = 30 B; SGD: p, g, v read, p, v and the copy written = 22 B)."""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from batchai_retinanet_horovod_coco_amd import models  # noqa: E402
+from batchai_retinanet_horovod_coco_amd.ops import native as N  # noqa: E402
+from batchai_retinanet_horovod_coco_amd.train.engine import Trainer  # noqa: E402
+from batchai_retinanet_horovod_coco_amd.train.optimizer import KerasAdam, KerasSGD  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=15)
+    ap.add_argument("--calls", type=int, default=20)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_optim.py times HIP kernels: it needs a GPU")
+    N.load(required=True)
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    tr = Trainer(models.backbone("resnet50").retinanet(80), compute_dtype=torch.bfloat16, device=dev)
+    flat, plan = tr.flat, tr.adam_plan()
+    assert tr.compute_weights is not None and plan.copy is not None
+    flat.grad.normal_()
+    scale = torch.full((), 1e-3, device=dev)
+    lr = 1e-6       # the weights stay finite however many steps are timed
+    forms = [
+        ("adam", 30, KerasAdam(flat, lr=lr)),
+        ("sgd plain", 22, KerasSGD(flat, lr=lr)),
+        ("sgd momentum", 22, KerasSGD(flat, lr=lr, momentum=0.9)),
+        ("sgd nesterov", 22, KerasSGD(flat, lr=lr, momentum=0.9, nesterov=True)),
+        ("sgd momentum+decay", 22, KerasSGD(flat, lr=lr, momentum=0.9, weight_decay=1e-4)),
+    ]
+    its = {name: 0 for name, _, _ in forms}
+
+    def run(name, opt, n):
+        # every form keeps its own step count; the plan's device counter is shared, so it is put right first
+        opt.iterations = its[name]
+        for _ in range(n):
+            opt.apply(scale)
+        its[name] = opt.iterations
+
+    for name, _, opt in forms:
+        run(name, opt, 3)
+    torch.cuda.synchronize()
+    times = {name: [] for name, _, _ in forms}
+    for _ in range(args.reps):
+        for name, _, opt in forms:
+            plan.sync_iter(its[name])
+            plan.set_lr(opt.base_lr(its[name] + 1))
+            if hasattr(opt, "momentum"):
+                plan.set_momentum(opt.momentum)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            run(name, opt, args.calls)
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(1e3 * e0.elapsed_time(e1) / args.calls)
+    assert bool(torch.isfinite(flat.data).all())
+    n = sum(s.numel for s in flat.segments)
+    print("R50 RetinaNet(80): {:,} parameters in {} segments, {} chunks; {} repetitions x {} steps per form"
+          .format(n, len(flat.segments), plan.nchunks, args.reps, args.calls))
+    print("{:<20} {:>10} {:>10} {:>10} {:>8} {:>9}".format("form", "median us", "min us", "max us", "B/elem", "TB/s"))
+    for name, nbytes, _ in forms:
+        t = sorted(times[name])
+        med = t[len(t) // 2]
+        print("{:<20} {:>10.1f} {:>10.1f} {:>10.1f} {:>8} {:>9.2f}".format(name, med, t[0], t[-1], nbytes,
+                                                                          n * nbytes / (med * 1e-6) / 1e12))
+    adam = sorted(times["adam"])
+    spread = adam[-1] - adam[0]
+    for name, _, _ in forms[1:]:
+        t = sorted(times[name])
+        d = t[len(t) // 2] - adam[len(adam) // 2]
+        print("{:<20} median {:+.1f} us against adam (adam's own spread over repetitions: {:.1f} us){}".format(
+            name, d, spread, "  SLOWER THAN ADAM BY MORE THAN THE SPREAD" if d > spread else ""))
+
+
+if __name__ == "__main__":
+    main()
