@@ -8,7 +8,7 @@ Same subcommands, flags, defaults and argument checks as ``/root/reference/train
 ``--no-evaluation``, ``--freeze-backbone``, ``--random-transform``, ``--image-min-side``,
 ``--image-max-side``), plus a ``synthetic`` dataset and MI355X options (``--dtype``, ``--clip-mode``,
 ``--bucket-mb``, ``--allreduce-dtype``, ``--workers``, ``--shard-data``, ``--checkpoint-format``,
-``--lr``, ``--clipnorm``, ``--optimizer``, ``--momentum``, ``--nesterov``, ``--weight-decay``, ``--warmup-epochs``, ``--seed``, ``--log-every``, ``--no-metric-average``, ``--log-all-ranks``,
+``--lr``, ``--clipnorm``, ``--optimizer``, ``--momentum``, ``--nesterov``, ``--weight-decay``, ``--ema-decay``, ``--weights-ema``, ``--warmup-epochs``, ``--seed``, ``--log-every``, ``--no-metric-average``, ``--log-all-ranks``,
 ``--metrics-jsonl``, ``--stop-on-nan``, ``--graph``, ``--graph-shapes``, ``--eval-batch-size``,
 ``--eval-pad-multiple``, ``--eval-workers``).
 
@@ -57,6 +57,16 @@ def check_args(parsed_args):
     resolve_optimizer(parsed_args)
     if getattr(parsed_args, "warmup_epochs", 0) < 0:
         raise SystemExit("--warmup-epochs must be >= 0")
+    if not 0.0 <= getattr(parsed_args, "ema_decay", 0.0) < 1.0:
+        raise SystemExit("--ema-decay must be in [0, 1) (0 turns the weight EMA off)")
+    if getattr(parsed_args, "weights_ema", False):
+        if not parsed_args.weights:
+            raise SystemExit("--weights-ema goes with --weights FILE: it loads that file's averaged weights")
+        if os.path.exists(parsed_args.weights):
+            from ..io import checkpoint
+            if not checkpoint.has_ema_weights(parsed_args.weights):
+                raise SystemExit("--weights-ema: {} holds no averaged weights (it was not written by a run with "
+                                 "--ema-decay)".format(parsed_args.weights))
     if "resnet" not in parsed_args.backbone:
         warnings.warn("Using experimental backbone {}. Only resnet50 has been properly tested.".format(
             parsed_args.backbone))
@@ -187,6 +197,14 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--nesterov", action="store_true", help="Nesterov momentum (--optimizer sgd).")
     parser.add_argument("--weight-decay", type=float, default=0.0,
                         help="Coupled L2 weight decay on the conv kernels, not on biases (--optimizer sgd only).")
+    parser.add_argument("--ema-decay", type=float, default=0.0, metavar="D",
+                        help="Keep an exponential moving average of the trainable weights, updated inside the fused "
+                             "optimizer launch with decay min(D, (1 + n) / (10 + n)) at its n-th update; the per-epoch "
+                             "evaluation runs on the average and snapshots store it as 'ema_weights'.  Default 0: "
+                             "off.")
+    parser.add_argument("--weights-ema", action="store_true",
+                        help="With --weights FILE: load the averaged weights the file holds (an error if it has "
+                             "none).")
     parser.add_argument("--warmup-epochs", type=float, default=0, metavar="E",
                         help="Horovod's gradual warmup over the first E epochs, from lr / ranks up to --lr "
                              "(--lr is the rate after the warmup).  Default 0: off.")
@@ -312,7 +330,9 @@ def create_callbacks(trainer, prediction_model, validation_generator, args):
             evaluation = CocoEval(validation_generator, tensorboard=tensorboard_callback, **batched)
         else:
             evaluation = Evaluate(validation_generator, tensorboard=tensorboard_callback, **batched)
-        callbacks.append(kc.RedirectModel(evaluation, prediction_model))
+        redirect = kc.RedirectModel(evaluation, prediction_model)
+        # with a weight EMA the evaluation sees the averaged weights (every rank: a sharded evaluation needs them all)
+        callbacks.append(kc.EmaWeights(redirect, trainer) if getattr(args, "ema_decay", 0.0) > 0 else redirect)
     if args.metrics_jsonl and rank == 0:
         callbacks.append(kc.JSONLMetrics(args.metrics_jsonl, every=args.log_every, batch_size=args.batch_size,
                                          world=runtime.size()))
@@ -428,7 +448,8 @@ def main(args=None):
         model = backbone.retinanet(train_generator.num_classes(),
                                    modifier=models.freeze if args.freeze_backbone else None)
         if weights is not None:
-            checkpoint.load_weights(model, weights, by_name=True, skip_mismatch=True)
+            checkpoint.load_weights(model, weights, by_name=True, skip_mismatch=True,
+                                    **(dict(group="ema_weights") if args.weights_ema else {}))
         elif args.calibrate_bn:
             from ..models.calibrate import calibrate_frozen_bn
             batch = train_generator.compute_input_output(train_generator.groups[0])
@@ -450,6 +471,7 @@ def main(args=None):
     trainer = Trainer(model, lr=args.lr, clipnorm=args.clipnorm, compute_dtype=dtype, clip_mode=args.clip_mode,
                       compression=comp, bucket_bytes=int(args.bucket_mb * 2 ** 20) if args.bucket_mb else None,
                       device=dev, overlap=not args.no_overlap,
+                      **(dict(ema_decay=args.ema_decay) if args.ema_decay > 0 else {}),
                       **(dict(optimizer="sgd", momentum=args.momentum, nesterov=args.nesterov,
                               weight_decay=args.weight_decay) if args.optimizer == "sgd" else {}))
     if args.snapshot is not None:

@@ -152,6 +152,66 @@ def _flat_slice(flat, p):
     return seg.offset, seg.numel
 
 
+EMA_GROUP = "ema_weights"
+EMA_PREFIX = "ema/"
+
+
+def _ema_of(optimizer) -> Optional[torch.Tensor]:
+    """The flat weight average of a live optimizer, None when it keeps none (``ema_decay`` 0)."""
+    return getattr(optimizer, "ema", None) if optimizer is not None else None
+
+
+def _ema_view(optimizer, t: torch.Tensor) -> torch.Tensor:
+    """The averaged value of ``t`` when it is a trainable parameter of the flat buffer, else ``t`` itself: with this
+    the averaged set is a complete weight set."""
+    seg = optimizer.flat.by_param.get(id(t))
+    if seg is None:
+        return t
+    return optimizer.ema[seg.offset:seg.offset + seg.numel].view(seg.shape)
+
+
+def _write_weight_group(g, model, pick=lambda t: t) -> None:
+    """A Keras ``model_weights``-layout group: ``layer_names``, per layer ``weight_names`` and the datasets."""
+    layers = keras_layers(model)
+    hdf5.save_attributes_to_hdf5_group(g, "layer_names", [n.encode() for n in layers])
+    g.attrs["backend"] = b"tensorflow"
+    g.attrs["keras_version"] = KERAS_VERSION.encode()
+    for lname, ws in layers.items():
+        lg = g.create_group(lname)
+        hdf5.save_attributes_to_hdf5_group(lg, "weight_names", [w[0].encode() for w in ws])
+        for wname, t, kind in ws:
+            a = _to_keras(_np(pick(t)), kind)
+            lg.create_dataset(wname, data=a.astype(np.float32))
+
+
+def _ema_missing(path: str, optimizer) -> None:
+    """A snapshot without an averaged set, loaded into a run that keeps one: the average starts from the weights
+    (one warning per load)."""
+    warnings.warn("{} holds no averaged weights ({}): the weight EMA starts from the loaded weights"
+                  .format(path, EMA_GROUP))
+    optimizer.seed_ema()
+
+
+def _restore_ema_h5(f, path: str, model, optimizer) -> None:
+    if _ema_of(optimizer) is None:
+        return                      # a run without --ema-decay ignores a stored average
+    if EMA_GROUP not in f:
+        _ema_missing(path, optimizer)
+        return
+    g = f[EMA_GROUP]
+    flat = optimizer.flat
+    with torch.no_grad():
+        for lname, ws in keras_layers(model).items():
+            for wname, t, kind in ws:
+                seg = flat.by_param.get(id(t))
+                if seg is None:
+                    continue
+                a = _from_keras(np.asarray(g[lname][wname]), kind)
+                optimizer.ema[seg.offset:seg.offset + seg.numel].copy_(
+                    torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(optimizer.ema.device))
+    optimizer.ema_start = int(optimizer.iterations) - int(np.asarray(g.attrs["ema_updates"]).reshape(-1)[0])
+
+
 def save_keras_h5(path: str, model, optimizer=None, epoch: Optional[int] = None, include_optimizer: bool = True) -> str:
     d = os.path.dirname(os.path.abspath(path))
     os.makedirs(d, exist_ok=True)
@@ -163,17 +223,13 @@ def save_keras_h5(path: str, model, optimizer=None, epoch: Optional[int] = None,
             f.attrs["training_config"] = json.dumps(training_config(optimizer)).encode()
         if epoch is not None:
             f.attrs["epoch"] = np.int64(epoch)
-        mw = f.create_group("model_weights")
-        layers = keras_layers(model)
-        hdf5.save_attributes_to_hdf5_group(mw, "layer_names", [n.encode() for n in layers])
-        mw.attrs["backend"] = b"tensorflow"
-        mw.attrs["keras_version"] = KERAS_VERSION.encode()
-        for lname, ws in layers.items():
-            g = mw.create_group(lname)
-            hdf5.save_attributes_to_hdf5_group(g, "weight_names", [w[0].encode() for w in ws])
-            for wname, t, kind in ws:
-                a = _to_keras(_np(t), kind)
-                g.create_dataset(wname, data=a.astype(np.float32))
+        _write_weight_group(f.create_group("model_weights"), model)
+        if include_optimizer and _ema_of(optimizer) is not None:
+            # the averaged set, laid out like model_weights (trainable tensors averaged, the others as they are)
+            eg = f.create_group(EMA_GROUP)
+            _write_weight_group(eg, model, lambda t: _ema_view(optimizer, t))
+            eg.attrs["ema_decay"] = np.float64(optimizer.ema_decay)
+            eg.attrs["ema_updates"] = np.int64(optimizer.ema_updates)
         if include_optimizer and optimizer is not None and hasattr(optimizer, "m"):
             ow = f.create_group("optimizer_weights")
             params = _keras_order_params(model)
@@ -208,8 +264,13 @@ def save_keras_h5(path: str, model, optimizer=None, epoch: Optional[int] = None,
     return path
 
 
-def _layer_weights_from_file(f) -> "OrderedDict[str, List[Tuple[str, np.ndarray]]]":
-    root = f["model_weights"] if "model_weights" in f else f
+def _layer_weights_from_file(f, group: str = "model_weights") -> "OrderedDict[str, List[Tuple[str, np.ndarray]]]":
+    if group in f:
+        root = f[group]
+    elif group == "model_weights":
+        root = f                    # a weights-only file
+    else:
+        raise ValueError("the file holds no group '{}'".format(group))
     names = hdf5.load_attributes_from_hdf5_group(root, "layer_names")
     out = OrderedDict()
     for ln in names:
@@ -219,12 +280,26 @@ def _layer_weights_from_file(f) -> "OrderedDict[str, List[Tuple[str, np.ndarray]
     return out
 
 
-def load_weights(model, path: str, by_name: bool = True, skip_mismatch: bool = False) -> List[str]:
-    """Keras ``load_weights`` (HDF5 or safetensors).  Returns the list of skipped weights."""
+def has_ema_weights(path: str) -> bool:
+    """Whether a checkpoint holds an averaged weight set (group ``ema_weights`` / tensors under ``ema/``)."""
     if path.endswith(".safetensors"):
-        return load_safetensors(model, path, optimizer=None, skip_mismatch=skip_mismatch)[1]
+        from safetensors import safe_open
+        with safe_open(path, framework="pt") as f:
+            return any(k.startswith(EMA_PREFIX) for k in f.keys())
+    return EMA_GROUP in hdf5.File(path, "r")
+
+
+def load_weights(model, path: str, by_name: bool = True, skip_mismatch: bool = False,
+                 group: str = "model_weights") -> List[str]:
+    """Keras ``load_weights`` (HDF5 or safetensors).  Returns the list of skipped weights.  ``group="ema_weights"``
+    loads the averaged set a run with a weight EMA stored; a ValueError when the file has none."""
+    if group not in ("model_weights", EMA_GROUP):
+        raise ValueError("group must be 'model_weights' or '{}', got {!r}".format(EMA_GROUP, group))
+    if path.endswith(".safetensors"):
+        return load_safetensors(model, path, optimizer=None, skip_mismatch=skip_mismatch,
+                                prefix=EMA_PREFIX if group == EMA_GROUP else "")[1]
     f = hdf5.File(path, "r")
-    file_layers = _layer_weights_from_file(f)
+    file_layers = _layer_weights_from_file(f, group)
     layers = keras_layers(model)
     skipped = []
     if not by_name:
@@ -282,6 +357,7 @@ def load_optimizer_h5(model, optimizer, path: str) -> bool:
                 a = _from_keras(np.asarray(ow[names[idx]]), kind)
                 off, num = _flat_slice(flat, p)
                 buf[off:off + num].copy_(torch.from_numpy(np.ascontiguousarray(a).reshape(-1)).to(buf.device))
+    _restore_ema_h5(f, path, model, optimizer)
     return True
 
 
@@ -343,6 +419,13 @@ def save_safetensors(path: str, model, optimizer=None, epoch: Optional[int] = No
         meta["iterations"] = str(int(optimizer.iterations))
         meta["lr"] = repr(float(optimizer.lr))
         meta["training_config"] = json.dumps(training_config(optimizer))
+    if _ema_of(optimizer) is not None:
+        params = dict(model.named_parameters())
+        for k, v in model.state_dict().items():
+            t = _ema_view(optimizer, params[k]) if k in params else v
+            tensors[EMA_PREFIX + k] = t.detach().contiguous().cpu().clone()
+        meta["ema_decay"] = repr(float(optimizer.ema_decay))
+        meta["ema_updates"] = str(int(optimizer.ema_updates))
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     tmp = path + ".tmp"
     save_file(tensors, tmp, metadata=meta)
@@ -350,14 +433,18 @@ def save_safetensors(path: str, model, optimizer=None, epoch: Optional[int] = No
     return path
 
 
-def load_safetensors(model, path: str, optimizer=None, skip_mismatch: bool = False):
+def load_safetensors(model, path: str, optimizer=None, skip_mismatch: bool = False, prefix: str = ""):
     """Returns (metadata, skipped tensors); ``metadata["optimizer_restored"]`` tells whether the optimizer state was
-    restored (only from a file written with the live optimizer's class)."""
+    restored (only from a file written with the live optimizer's class).  ``prefix="ema/"`` loads the averaged set."""
     from safetensors.torch import load_file
     from safetensors import safe_open
     sd = load_file(path)
     with safe_open(path, framework="pt") as f:
         meta = f.metadata() or {}
+    if prefix:
+        if not any(k.startswith(prefix) for k in sd):
+            raise ValueError("the file holds no tensors under '{}'".format(prefix))
+        sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
     own = model.state_dict()
     skipped = []
     with torch.no_grad():
@@ -370,7 +457,7 @@ def load_safetensors(model, path: str, optimizer=None, skip_mismatch: bool = Fal
             v.copy_(sd[k].to(v.device, v.dtype))
         restored = False
         if optimizer is not None and not _class_mismatch(path, optimizer):
-            state = optimizer.state_tensors()
+            state = {k: t for k, t in optimizer.state_tensors().items() if k != "ema"}     # the average: below
             keys = ["__optimizer__." + k for k in state]
             if all(k in sd and sd[k].numel() == t.numel() for k, t in zip(keys, state.values())):
                 for k, t in zip(keys, state.values()):
@@ -379,6 +466,17 @@ def load_safetensors(model, path: str, optimizer=None, skip_mismatch: bool = Fal
                 if "lr" in meta:
                     optimizer.lr = float(meta["lr"])
                 restored = True
+                if _ema_of(optimizer) is not None:
+                    params = dict(model.named_parameters())
+                    if all(EMA_PREFIX + k in sd for k in params) and "ema_updates" in meta:
+                        for k, prm in params.items():
+                            seg = optimizer.flat.by_param.get(id(prm))
+                            if seg is not None:
+                                optimizer.ema[seg.offset:seg.offset + seg.numel].copy_(
+                                    sd[EMA_PREFIX + k].reshape(-1).to(optimizer.ema.device))
+                        optimizer.ema_start = optimizer.iterations - int(meta["ema_updates"])
+                    else:
+                        _ema_missing(path, optimizer)
     meta = dict(meta, optimizer_restored=restored)
     return meta, skipped
 

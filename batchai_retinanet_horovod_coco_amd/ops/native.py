@@ -53,6 +53,11 @@ _SIGS = {
                       c_float, c_vp],
     "mxr_sgd_step": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp],
     "mxr_refresh_copy": [c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp],
+    "mxr_adam_step_ema": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_float,
+                          c_float, c_float, c_float, c_ll, c_vp],
+    "mxr_sgd_step_ema": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int,
+                         c_float, c_ll, c_vp],
+    "mxr_swap_refresh": [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp],
     "mxr_grad_norm_clip": [c_vp, c_ll, c_vp, c_float, c_float, c_float, c_vp, c_vp],
     "mxr_scale_inplace": [c_vp, c_ll, c_vp, c_vp],
     "mxr_norm_grid": [],
@@ -386,7 +391,8 @@ def anchor_targets(anchors, gt, gt_count, image_hw, neg=0.4, pos=0.5, std=0.2, c
 # optimizer
 # =========================================================================================
 class AdamPlan:
-    """Device-side chunk/segment tables for the fused multi-tensor Keras-Adam kernel."""
+    """Device-side chunk/segment tables for the fused multi-tensor Keras-Adam kernel.  ``hyper``: [0] lr_t (Adam's
+    prologue), [1] lr, [2] momentum (SGD), [3] the weight EMA's decay of this step (the EMA forms' prologue)."""
 
     CHUNK = 8192
 
@@ -729,24 +735,45 @@ def adam_plan(flat) -> AdamPlan:
     return p
 
 
-def adam_step(flat, m, v, grad_scale, lr, iteration, b1, b2, eps, plan: Optional[AdamPlan] = None):
-    """Fused Keras-Adam on the flat buffers.  ``lr`` is the base lr (lr_t is computed on device)."""
+def _check_ema(flat, ema, ema_decay, name):
+    if ema.shape != flat.data.shape or ema.dtype != torch.float32 or ema.device != flat.data.device \
+            or not ema.is_contiguous():
+        raise ValueError("{}: ema must be a contiguous fp32 buffer shaped like the flat weights, on their device"
+                         .format(name))
+    if not 0.0 < ema_decay < 1.0:
+        raise ValueError("{}: ema_decay must be in (0, 1) with an ema buffer, got {!r}".format(name, ema_decay))
+
+
+def adam_step(flat, m, v, grad_scale, lr, iteration, b1, b2, eps, plan: Optional[AdamPlan] = None, ema=None,
+              ema_decay: float = 0.0, ema_start: int = 0):
+    """Fused Keras-Adam on the flat buffers.  ``lr`` is the base lr (lr_t is computed on device).  With ``ema`` (an
+    fp32 buffer shaped like ``flat.data``) the same launch also carries the weights' moving average; its decay of
+    this step comes from the device step counter (``hyper[3]``, written by the prologue)."""
     plan = plan or adam_plan(flat)
     plan.set_lr(lr)
     plan.sync_iter(iteration)
     plan.host_iter = iteration + 1
     gs = grad_scale.reshape(1).float().contiguous() if torch.is_tensor(grad_scale) else \
         torch.full((1,), float(grad_scale), device=flat.data.device)
-    _chk(lib().mxr_adam_step(_p(flat.data), _p(flat.grad), _p(m), _p(v), _p(plan.copy), _p(plan.scales),
-                             _p(plan.chunks), plan.nchunks, _p(plan.segs), _p(gs), _p(plan.hyper), _p(plan.iter),
-                             b1, b2, eps, _s()), "adam")
+    if ema is None:
+        _chk(lib().mxr_adam_step(_p(flat.data), _p(flat.grad), _p(m), _p(v), _p(plan.copy), _p(plan.scales),
+                                 _p(plan.chunks), plan.nchunks, _p(plan.segs), _p(gs), _p(plan.hyper), _p(plan.iter),
+                                 b1, b2, eps, _s()), "adam")
+    else:
+        _check_ema(flat, ema, ema_decay, "adam_step")
+        _chk(lib().mxr_adam_step_ema(_p(flat.data), _p(flat.grad), _p(m), _p(v), _p(ema), _p(plan.copy),
+                                     _p(plan.scales), _p(plan.chunks), plan.nchunks, _p(plan.segs), _p(gs),
+                                     _p(plan.hyper), _p(plan.iter), b1, b2, eps, ema_decay, int(ema_start), _s()),
+             "adam_ema")
     plan.generation += 1     # the compute copies changed (ComputeWeights.flipped re-flips lazily)
 
 
-def sgd_step(flat, v, grad_scale, lr, momentum, iteration, nesterov, seg_wd, plan: Optional[AdamPlan] = None):
+def sgd_step(flat, v, grad_scale, lr, momentum, iteration, nesterov, seg_wd, plan: Optional[AdamPlan] = None,
+             ema=None, ema_decay: float = 0.0, ema_start: int = 0):
     """Fused Keras-SGD (momentum, nesterov, coupled weight decay) on the flat buffers, over the flat buffer's
     :class:`AdamPlan` tables.  ``lr`` is the learning rate of this step (``decay`` applied); it and ``momentum`` are
-    read from device memory.  ``seg_wd``: one fp32 decay factor per segment on the device, or None for no decay."""
+    read from device memory.  ``seg_wd``: one fp32 decay factor per segment on the device, or None for no decay.
+    ``ema``: as in :func:`adam_step`."""
     plan = plan or adam_plan(flat)
     plan.set_lr(lr)
     plan.set_momentum(momentum)
@@ -757,10 +784,29 @@ def sgd_step(flat, v, grad_scale, lr, momentum, iteration, nesterov, seg_wd, pla
         raise ValueError("sgd_step: seg_wd must hold one fp32 value per segment on the parameters' device")
     gs = grad_scale.reshape(1).float().contiguous() if torch.is_tensor(grad_scale) else \
         torch.full((1,), float(grad_scale), device=flat.data.device)
-    _chk(lib().mxr_sgd_step(_p(flat.data), _p(flat.grad), _p(v), _p(plan.copy), _p(plan.scales), _p(plan.chunks),
-                            plan.nchunks, _p(plan.segs), _p(seg_wd), _p(gs), _p(plan.hyper), _p(plan.iter),
-                            1 if nesterov else 0, _s()), "sgd")
+    if ema is None:
+        _chk(lib().mxr_sgd_step(_p(flat.data), _p(flat.grad), _p(v), _p(plan.copy), _p(plan.scales), _p(plan.chunks),
+                                plan.nchunks, _p(plan.segs), _p(seg_wd), _p(gs), _p(plan.hyper), _p(plan.iter),
+                                1 if nesterov else 0, _s()), "sgd")
+    else:
+        _check_ema(flat, ema, ema_decay, "sgd_step")
+        _chk(lib().mxr_sgd_step_ema(_p(flat.data), _p(flat.grad), _p(v), _p(ema), _p(plan.copy), _p(plan.scales),
+                                    _p(plan.chunks), plan.nchunks, _p(plan.segs), _p(seg_wd), _p(gs), _p(plan.hyper),
+                                    _p(plan.iter), 1 if nesterov else 0, ema_decay, int(ema_start), _s()), "sgd_ema")
     plan.generation += 1     # the compute copies changed (ComputeWeights.flipped re-flips lazily)
+
+
+def swap_refresh(flat, ema, plan: Optional[AdamPlan] = None):
+    """Exchange the weights and their moving average element by element and rewrite the bf16 compute copies of the
+    new weights, in one pass over the chunk table and without a temporary.  No pointer moves; ``generation`` advances,
+    so the flipped, hx32-packed and fp8 copies rebuild at their next use."""
+    plan = plan or adam_plan(flat)
+    if ema.shape != flat.data.shape or ema.dtype != torch.float32 or ema.device != flat.data.device \
+            or not ema.is_contiguous():
+        raise ValueError("swap_refresh: ema must be a contiguous fp32 buffer shaped like the flat weights")
+    _chk(lib().mxr_swap_refresh(_p(flat.data), _p(ema), _p(plan.copy), _p(plan.scales), _p(plan.chunks),
+                                plan.nchunks, _p(plan.segs), _s()), "swap_refresh")
+    plan.generation += 1
 
 
 NORM_GRID = 1024

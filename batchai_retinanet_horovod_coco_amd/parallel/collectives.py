@@ -292,8 +292,12 @@ def broadcast_optimizer_state(optimizer, root_rank: int = 0) -> None:
         return
     with torch.no_grad():
         _coalesced_broadcast(list(optimizer.state_tensors().values()), root_rank)
-    it = broadcast_object(getattr(optimizer, "iterations", 0), root_rank)
+    # the weight EMA's update count is iterations - ema_start: the two travel together
+    it, ema_start = broadcast_object((getattr(optimizer, "iterations", 0), getattr(optimizer, "ema_start", 0)),
+                                     root_rank)
     optimizer.iterations = it
+    if hasattr(optimizer, "ema_start"):
+        optimizer.ema_start = ema_start
     lr = broadcast_object(getattr(optimizer, "lr", None), root_rank)
     if lr is not None:
         optimizer.lr = lr

@@ -320,6 +320,36 @@ class RedirectModel(Callback):
         self.callback.on_train_end(logs)
 
 
+class EmaWeights(Callback):
+    """Run ``callback``'s ``on_epoch_end`` (the evaluation) on the averaged weights: inside
+    ``trainer.ema_weights()``, on every rank, so a rank-sharded evaluation sees the same weights everywhere.
+    Everything else passes through.  The checkpoint callback is not wrapped: ``model_weights`` stay the raw
+    training weights, the averaged set goes into its own group."""
+
+    def __init__(self, callback: Callback, trainer):
+        super().__init__()
+        self.callback = callback
+        self.trainer = trainer
+
+    def set_params(self, params):
+        super().set_params(params)
+        self.callback.set_params(params)
+
+    def set_model(self, model):
+        super().set_model(model)
+        self.callback.set_model(model)
+
+    def on_epoch_begin(self, epoch, logs=None): self.callback.on_epoch_begin(epoch, logs)
+    def on_batch_begin(self, batch, logs=None): self.callback.on_batch_begin(batch, logs)
+    def on_batch_end(self, batch, logs=None): self.callback.on_batch_end(batch, logs)
+    def on_train_begin(self, logs=None): self.callback.on_train_begin(logs)
+    def on_train_end(self, logs=None): self.callback.on_train_end(logs)
+
+    def on_epoch_end(self, epoch, logs=None):
+        with self.trainer.ema_weights():
+            self.callback.on_epoch_end(epoch, logs)
+
+
 class CSVLogger(Callback):
     def __init__(self, filename: str, append: bool = False):
         super().__init__()

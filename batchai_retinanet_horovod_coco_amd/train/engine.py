@@ -13,6 +13,7 @@ This is CS3 of the survey (the hot loop of ``fit_generator`` driven from
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import Dict, Optional
 
@@ -52,7 +53,8 @@ class Trainer:
     def __init__(self, model, lr: float = 1e-5, clipnorm: float = 0.001, compute_dtype: torch.dtype = torch.float32,
                  clip_mode: str = "local", compression=None, bucket_bytes: Optional[int] = None,
                  device: Optional[torch.device] = None, overlap: bool = True, target_backend: str = "auto",
-                 optimizer: str = "adam", momentum: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0):
+                 optimizer: str = "adam", momentum: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0,
+                 ema_decay: float = 0.0):
         from ..parallel.collectives import Compression
         self.device = device or (runtime.device() if runtime.is_initialized() else torch.device("cpu"))
         self.model = model.to(self.device)
@@ -61,10 +63,10 @@ class Trainer:
         if optimizer == "adam":
             if momentum or nesterov or weight_decay:
                 raise ValueError("momentum, nesterov and weight_decay belong to optimizer='sgd'")
-            self.base_optimizer = KerasAdam(self.flat, lr=lr, clipnorm=clipnorm)
+            self.base_optimizer = KerasAdam(self.flat, lr=lr, clipnorm=clipnorm, ema_decay=ema_decay)
         elif optimizer == "sgd":
             self.base_optimizer = KerasSGD(self.flat, lr=lr, momentum=momentum, nesterov=nesterov,
-                                           weight_decay=weight_decay, clipnorm=clipnorm)
+                                           weight_decay=weight_decay, clipnorm=clipnorm, ema_decay=ema_decay)
         else:
             raise ValueError("optimizer must be 'adam' or 'sgd', got {!r}".format(optimizer))
         self.optimizer = DistributedOptimizer(self.base_optimizer, compression=compression or Compression.none,
@@ -76,6 +78,7 @@ class Trainer:
         self.shapes_callback = None
         self.last_logs: Dict[str, torch.Tensor] = {}
         self.compute_weights = None
+        self._ema_swapped = False   # inside ema_weights(): flat.data holds the average, the EMA buffer the weights
         from ..ops import native
         # zero-padded gradient rows of the two final layers: one buffer per shape a captured step holds plus a
         # floating one (a graph keeps the pointer it was captured with)
@@ -203,6 +206,8 @@ class Trainer:
             # (Module.train() walks all ~150 modules: ~0.9 ms of host time, which sat in front of the
             # step's first kernels every step when called unconditionally)
             self.model.train()
+        if self._ema_swapped:
+            raise RuntimeError("train_on_batch inside ema_weights(): the averaged weights are in place")
         if self.step_graphs is not None:
             return self.step_graphs.step(images, gt, gt_count, image_hw)
         return self._train_on_batch(images, gt, gt_count, image_hw)
@@ -339,5 +344,38 @@ class Trainer:
         if self.step_graphs is not None:
             self.step_graphs.invalidate()       # the flat buffers are rebound and the compute copies rebuilt
         self.flat.rebind()
+        if self.base_optimizer.ema is not None and self.base_optimizer.ema_updates == 0:
+            # a run that has not averaged yet (--weights / --imagenet-weights / broadcast): the average starts from
+            # the weights as they are now; a restored average is left alone
+            self.base_optimizer.seed_ema()
         if self.compute_weights is not None:
             self.compute_weights.build()     # BN scales may have changed too
+
+    # ---------------------------------------------------------------- weight EMA
+    def _swap_ema(self) -> None:
+        opt = self.base_optimizer
+        if opt._use_hip():
+            from ..ops import native
+            native.swap_refresh(self.flat, opt.ema)     # one pass: exchange + the bf16 compute copies
+        else:
+            tmp = self.flat.data.clone()
+            self.flat.data.copy_(opt.ema)
+            opt.ema.copy_(tmp)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the body on the averaged weights (evaluation): on entry the weights and their moving average are
+        exchanged in place, on exit exchanged back.  No pointer moves, so captured step graphs stay valid and
+        ``on_weights_changed`` is not called.  Only the trainable parameters are averaged; everything else (frozen
+        BN statistics, live BN buffers) is what it is.  Not reentrant, and no training step inside."""
+        if self.base_optimizer.ema is None:
+            raise RuntimeError("ema_weights: this trainer keeps no weight EMA (ema_decay=0)")
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights: already inside (the averaged weights are in place)")
+        self._swap_ema()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self._ema_swapped = False

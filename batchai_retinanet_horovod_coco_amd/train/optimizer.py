@@ -18,6 +18,12 @@ factor and lr_t live on the device so a step never synchronises with the host.
 :class:`KerasSGD` (Keras 2 ``SGD(lr, momentum, decay, nesterov)`` plus coupled weight decay) shares the norm, the
 clip factor and the backend choice with it (:class:`_FlatOptimizer`) and runs as one fused launch too
 (``mxr_sgd_step``).
+
+Both take ``ema_decay = D`` (0 < D < 1; 0, the default, is off): an fp32 exponential moving average of the flat
+weights, seeded with a copy of them and updated after every step, ``ema = d_n * ema + (1 - d_n) * p_new`` with
+``d_n = min(D, (1 + n) / (10 + n))`` in fp32 and ``n = iterations + 1 - ema_start`` the 1-based index of the update.
+On the GPU the EMA forms of the same fused launches carry it (``mxr_adam_step_ema`` / ``mxr_sgd_step_ema``; the decay
+is derived on the device from the step counter, so a replayed graph sees a new one each step).
 """
 from __future__ import annotations
 
@@ -37,7 +43,10 @@ class _FlatOptimizer:
 
     class_name = ""
 
-    def __init__(self, flat: FlatParams, lr: float, decay: float, clipnorm: Optional[float], backend: str):
+    def __init__(self, flat: FlatParams, lr: float, decay: float, clipnorm: Optional[float], backend: str,
+                 ema_decay: float = 0.0):
+        if not 0.0 <= ema_decay < 1.0:
+            raise ValueError("ema_decay must be in [0, 1), got {!r}".format(ema_decay))
         self.flat = flat
         self.lr = float(lr)
         self.initial_lr = float(lr)
@@ -46,6 +55,48 @@ class _FlatOptimizer:
         self.iterations = 0                       # host mirror (the step count is deterministic)
         self.backend = backend
         self._dev = flat.data.device
+        # exponential moving average of the weights, carried by the same fused launch (0: off, no buffer)
+        self.ema_decay = float(ema_decay)
+        self.ema_start = 0                        # ``iterations`` when the average was seeded
+        self.ema = flat.data.detach().clone() if self.ema_decay > 0 else None
+
+    # -------------------------------------------------------------- weight EMA
+    @property
+    def ema_updates(self) -> int:
+        """EMA updates so far: derived from the step count, there is no counter of its own."""
+        return self.iterations - self.ema_start
+
+    def ema_decay_at(self, n: int) -> float:
+        """``d_n = min(D, (1 + n) / (10 + n))`` of the ``n``-th EMA update (1-based), in fp32 arithmetic: TensorFlow's
+        ``ExponentialMovingAverage(num_updates)`` ramp, which the fused kernels' prologue evaluates on the device."""
+        import numpy as np
+        d = np.float32(1 + n) / np.float32(10 + n)
+        return float(min(np.float32(self.ema_decay), d))
+
+    def seed_ema(self) -> None:
+        """Start the average over: a copy of the weights as they are, no update counted."""
+        if self.ema is not None:
+            self.ema.copy_(self.flat.data)
+            self.ema_start = self.iterations
+
+    def _ema_torch(self) -> None:
+        """The torch expression of the EMA update that follows this step's weight update (``iterations`` not yet
+        advanced)."""
+        if self.ema is not None:
+            d = self.ema_decay_at(self.iterations + 1 - self.ema_start)
+            self.ema.mul_(d).add_(self.flat.data, alpha=1.0 - d)
+
+    def _ema_config(self) -> Dict:
+        return {"ema_decay": self.ema_decay} if self.ema is not None else {}
+
+    def _ema_state(self) -> Dict:
+        return {"ema": self.ema} if self.ema is not None else {}
+
+    def _ema_args(self) -> Dict:
+        """What the fused step takes for the EMA form (empty: the plain entry point)."""
+        if self.ema is None:
+            return {}
+        return {"ema": self.ema, "ema_decay": self.ema_decay, "ema_start": self.ema_start}
 
     def _use_hip(self) -> bool:
         from ..ops import native
@@ -100,21 +151,21 @@ class KerasAdam(_FlatOptimizer):
 
     def __init__(self, flat: FlatParams, lr: float = 1e-5, beta_1: float = 0.9, beta_2: float = 0.999,
                  epsilon: float = 1e-7, decay: float = 0.0, clipnorm: Optional[float] = 0.001,
-                 amsgrad: bool = False, backend: str = "auto"):
+                 amsgrad: bool = False, backend: str = "auto", ema_decay: float = 0.0):
         if amsgrad:
             raise NotImplementedError("amsgrad is off in the reference optimizer")
-        super().__init__(flat, lr, decay, clipnorm, backend)
+        super().__init__(flat, lr, decay, clipnorm, backend, ema_decay)
         self.beta_1, self.beta_2, self.epsilon = beta_1, beta_2, epsilon
         self.m = torch.zeros_like(flat.data)
         self.v = torch.zeros_like(flat.data)
 
     # -------------------------------------------------------------- keras-ish API
     def get_config(self) -> Dict:
-        return {"lr": self.lr, "beta_1": self.beta_1, "beta_2": self.beta_2, "decay": self.decay,
-                "epsilon": self.epsilon, "amsgrad": False, "clipnorm": self.clipnorm}
+        return dict({"lr": self.lr, "beta_1": self.beta_1, "beta_2": self.beta_2, "decay": self.decay,
+                     "epsilon": self.epsilon, "amsgrad": False, "clipnorm": self.clipnorm}, **self._ema_config())
 
     def state_tensors(self):
-        return {"m": self.m, "v": self.v}
+        return dict({"m": self.m, "v": self.v}, **self._ema_state())
 
     def lr_t(self, t: int) -> float:
         lr = self.base_lr(t)
@@ -127,12 +178,13 @@ class KerasAdam(_FlatOptimizer):
         if self._use_hip():
             from ..ops import native
             native.adam_step(self.flat, self.m, self.v, grad_scale, self.base_lr(t), self.iterations, self.beta_1, self.beta_2,
-                             self.epsilon)
+                             self.epsilon, **self._ema_args())
         else:
             g = self.flat.grad * grad_scale
             self.m.mul_(self.beta_1).add_(g, alpha=1 - self.beta_1)
             self.v.mul_(self.beta_2).addcmul_(g, g, value=1 - self.beta_2)
             self.flat.data.addcdiv_(self.m, self.v.sqrt().add_(self.epsilon), value=-lr_t)
+            self._ema_torch()
         self.iterations = t
 
 
@@ -152,10 +204,10 @@ class KerasSGD(_FlatOptimizer):
 
     def __init__(self, flat: FlatParams, lr: float = 0.01, momentum: float = 0.0, decay: float = 0.0,
                  nesterov: bool = False, weight_decay: float = 0.0, clipnorm: Optional[float] = None,
-                 backend: str = "auto"):
+                 backend: str = "auto", ema_decay: float = 0.0):
         if momentum < 0 or weight_decay < 0:
             raise ValueError("momentum and weight_decay must be >= 0")
-        super().__init__(flat, lr, decay, clipnorm, backend)
+        super().__init__(flat, lr, decay, clipnorm, backend, ema_decay)
         self.momentum = float(momentum)
         self.nesterov = bool(nesterov)
         self.weight_decay = float(weight_decay)
@@ -166,11 +218,11 @@ class KerasSGD(_FlatOptimizer):
             self.seg_wd()           # built now: a captured step must not meet its first upload
 
     def get_config(self) -> Dict:
-        return {"lr": self.lr, "momentum": self.momentum, "decay": self.decay, "nesterov": self.nesterov,
-                "clipnorm": self.clipnorm, "weight_decay": self.weight_decay}
+        return dict({"lr": self.lr, "momentum": self.momentum, "decay": self.decay, "nesterov": self.nesterov,
+                     "clipnorm": self.clipnorm, "weight_decay": self.weight_decay}, **self._ema_config())
 
     def state_tensors(self):
-        return {"velocity": self.velocity}
+        return dict({"velocity": self.velocity}, **self._ema_state())
 
     def segment_decay(self):
         """``weight_decay`` for the segments of rank >= 2, 0 for the others: one value per segment."""
@@ -200,7 +252,7 @@ class KerasSGD(_FlatOptimizer):
         if self._use_hip():
             from ..ops import native
             native.sgd_step(self.flat, self.velocity, grad_scale, lr_t, self.momentum, self.iterations, self.nesterov,
-                            self.seg_wd())
+                            self.seg_wd(), **self._ema_args())
         else:
             g = self.flat.grad * grad_scale
             if self.weight_decay != 0.0:
@@ -210,4 +262,5 @@ class KerasSGD(_FlatOptimizer):
                 self.flat.data.add_(self.velocity, alpha=self.momentum).add_(g, alpha=-lr_t)
             else:
                 self.flat.data.add_(self.velocity)
+            self._ema_torch()
         self.iterations = t

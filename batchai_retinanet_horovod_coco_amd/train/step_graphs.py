@@ -21,6 +21,10 @@ captured step per shape class and stays bit-identical to the eager run:
 * **learning rate**: written before every replay through ``AdamPlan.set_lr`` (outside the graph), from the same
   expression the eager ``KerasAdam.apply`` uses (``KerasAdam.base_lr``).  ``KerasSGD``'s momentum goes the same way
   (``AdamPlan.set_momentum``).
+* **weight EMA** (``ema_decay``): nothing is written before a replay.  The decay cap and ``ema_start`` are by-value
+  constants of the captured launch and the decay of each update is derived on the device from the step counter the
+  replay advances; a restore that changes them goes through ``on_weights_changed``, which drops every graph.
+  ``Trainer.ema_weights()`` exchanges weights and average in place between steps: no pointer moves, no graph goes.
 * **lifetime**: the persistent zero-padded gradient rows a captured step writes (``ops.native.ShapeSlots``) are
   pinned while its graph lives; ``Trainer.on_weights_changed`` drops every graph and the classes start over.
 * **failure**: a capture that raises, or one in which the conv tuner met a key it still has to race, is thrown

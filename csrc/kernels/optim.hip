@@ -11,6 +11,12 @@
 //   g_eff = g * grad_scale + wd[seg] * p ;  v = momentum * v - lr * g_eff ;
 //   p += v   (nesterov: p += momentum * v - lr * g_eff)
 // with lr = hyper[1] and momentum = hyper[2] read from device memory (a replayed graph sees a changed value).
+//
+// Weight EMA (the EMA forms of both kernels, a compile-time parameter): after p_new the same thread loads the
+// matching elements of the fp32 average and stores  ema = d * ema + (1 - d) * p_new,  with
+//   d = hyper[3] = min(D, (1 + n) / (10 + n)),  n = *iter + 1 - ema_start  (1-based index of this EMA update),
+// written by a one-thread prologue that reads the step counter BEFORE this step advances it: a replayed graph gets
+// a new d every step.  mxr_swap_refresh exchanges weights and average in place (evaluation on the average).
 #include "common.h"
 
 namespace {
@@ -29,16 +35,32 @@ struct Seg {
 
 constexpr int kBlock = 256;
 
-__global__ void adam_prologue(float* hyper, long long* iter, float b1, float b2) {
+// d_n of the EMA update that follows the step which takes the counter from `it` to `it + 1` (fp32, as the host
+// mirror KerasAdam.ema_decay_at computes it).
+__device__ __forceinline__ float ema_decay_of(long long it, float D, long long ema_start) {
+  const long long n = it + 1 - ema_start;
+  return fminf(D, __fdiv_rn((float)(1 + n), (float)(10 + n)));
+}
+
+// SGD's EMA forms: one thread, launched in front of sgd_kernel (whose block 0 advances *iter during the launch).
+__global__ void ema_prologue(float* hyper, const long long* iter, float D, long long ema_start) {
+  hyper[3] = ema_decay_of(*iter, D, ema_start);
+}
+
+template <bool EMA>
+__global__ void adam_prologue(float* hyper, long long* iter, float b1, float b2, float D, long long ema_start) {
+  if (EMA) hyper[3] = ema_decay_of(*iter, D, ema_start);
   const long long t = *iter + 1;
   const float lr = hyper[1];
   hyper[0] = lr * sqrtf(1.f - powf(b2, (float)t)) / (1.f - powf(b1, (float)t));
   *iter = t;
 }
 
+template <bool EMA>
 __global__ __launch_bounds__(kBlock) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                       float* __restrict__ m, float* __restrict__ v,
-                                                      bf16_t* __restrict__ wcopy, const float* __restrict__ scales,
+                                                      float* __restrict__ ema, bf16_t* __restrict__ wcopy,
+                                                      const float* __restrict__ scales,
                                                       const Chunk* __restrict__ chunks, const Seg* __restrict__ segs,
                                                       const float* __restrict__ grad_scale,
                                                       const float* __restrict__ hyper, float b1, float b2, float eps) {
@@ -46,6 +68,7 @@ __global__ __launch_bounds__(kBlock) void adam_kernel(float* __restrict__ p, con
   const Seg s = segs[c.seg];
   const float gs = *grad_scale;
   const float lr_t = hyper[0];
+  const float d = EMA ? hyper[3] : 0.f;
   const long long base = c.start;
   // chunk starts are 4-aligned (segments are 64-aligned, chunk length multiple of 4)
   const int nv = c.len >> 2;
@@ -66,6 +89,13 @@ __global__ __launch_bounds__(kBlock) void adam_kernel(float* __restrict__ p, con
     *reinterpret_cast<float4*>(p + e) = pp;
     *reinterpret_cast<float4*>(m + e) = mm;
     *reinterpret_cast<float4*>(v + e) = vv;
+    if (EMA) {
+      float4 ee = *reinterpret_cast<const float4*>(ema + e);
+      float* ea = &ee.x;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ea[j] = d * ea[j] + (1.f - d) * pa[j];
+      *reinterpret_cast<float4*>(ema + e) = ee;
+    }
     if (s.has_copy) {
       const long long le = e - s.offset;
       ushort4 w;
@@ -93,6 +123,15 @@ __global__ __launch_bounds__(kBlock) void adam_kernel(float* __restrict__ p, con
       wcopy[e] = f2bf(pj * sc);
     }
   }
+  // The average's tail is a loop of its own, over the elements this thread has just written: inside the loop above
+  // the compiler pairs its multiply-add with the update's (packed fp32 math) and un-fuses the update's fma on the
+  // way, and the EMA forms must update p and the slots bit for bit as the plain forms do.
+  if (EMA) {
+    for (int i = (nv << 2) + threadIdx.x; i < c.len; i += kBlock) {
+      const long long e = base + i;
+      ema[e] = d * ema[e] + (1.f - d) * p[e];
+    }
+  }
 }
 
 // One element of the SGD update; returns the new parameter, updates the velocity in place.
@@ -104,9 +143,10 @@ __device__ __forceinline__ float sgd_elem(float p, float g, float& v, float gs, 
   return NESTEROV ? p + mom * v - lr * ge : p + v;
 }
 
-template <bool NESTEROV, bool DECAY>
+template <bool NESTEROV, bool DECAY, bool EMA>
 __global__ __launch_bounds__(kBlock) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                     float* __restrict__ v, bf16_t* __restrict__ wcopy,
+                                                     float* __restrict__ v, float* __restrict__ ema,
+                                                     bf16_t* __restrict__ wcopy,
                                                      const float* __restrict__ scales, const Chunk* __restrict__ chunks,
                                                      const Seg* __restrict__ segs, const float* __restrict__ seg_wd,
                                                      const float* __restrict__ grad_scale,
@@ -117,6 +157,7 @@ __global__ __launch_bounds__(kBlock) void sgd_kernel(float* __restrict__ p, cons
   const float lr = hyper[1];
   const float mom = hyper[2];
   const float wd = DECAY ? seg_wd[c.seg] : 0.f;
+  const float d = EMA ? hyper[3] : 0.f;     // ema_prologue wrote it from the counter as it stood before this launch
   // the step counter: nothing in this launch reads it
   if (blockIdx.x == 0 && threadIdx.x == 0) *iter = *iter + 1;
   const long long base = c.start;
@@ -131,6 +172,13 @@ __global__ __launch_bounds__(kBlock) void sgd_kernel(float* __restrict__ p, cons
     for (int j = 0; j < 4; ++j) pa[j] = sgd_elem<NESTEROV, DECAY>(pa[j], ga[j], va[j], gs, wd, lr, mom);
     *reinterpret_cast<float4*>(p + e) = pp;
     *reinterpret_cast<float4*>(v + e) = vv;
+    if (EMA) {
+      float4 ee = *reinterpret_cast<const float4*>(ema + e);
+      float* ea = &ee.x;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ea[j] = d * ea[j] + (1.f - d) * pa[j];
+      *reinterpret_cast<float4*>(ema + e) = ee;
+    }
     if (s.has_copy) {
       const long long le = e - s.offset;
       ushort4 w;
@@ -156,6 +204,13 @@ __global__ __launch_bounds__(kBlock) void sgd_kernel(float* __restrict__ p, cons
       wcopy[e] = f2bf(pj * sc);
     }
   }
+  // the average's tail: a loop of its own, as in adam_kernel
+  if (EMA) {
+    for (int i = (nv << 2) + threadIdx.x; i < c.len; i += kBlock) {
+      const long long e = base + i;
+      ema[e] = d * ema[e] + (1.f - d) * p[e];
+    }
+  }
 }
 
 // Refresh only the bf16 compute copy (after loading weights / broadcast).
@@ -170,6 +225,46 @@ __global__ __launch_bounds__(kBlock) void copy_kernel(const float* __restrict__ 
     float sc = 1.f;
     if (s.scale_off >= 0) sc = scales[s.scale_off + (e - s.offset) / s.row_len];
     wcopy[e] = f2bf(p[e] * sc);
+  }
+}
+
+// Exchange the weights and their moving average in place and write the bf16 compute copy of the new weights.
+__global__ __launch_bounds__(kBlock) void swap_kernel(float* __restrict__ p, float* __restrict__ ema,
+                                                      bf16_t* __restrict__ wcopy, const float* __restrict__ scales,
+                                                      const Chunk* __restrict__ chunks, const Seg* __restrict__ segs) {
+  const Chunk c = chunks[blockIdx.x];
+  const Seg s = segs[c.seg];
+  const long long base = c.start;
+  const int nv = c.len >> 2;
+  for (int i = threadIdx.x; i < nv; i += kBlock) {
+    const long long e = base + 4LL * i;
+    const float4 pp = *reinterpret_cast<const float4*>(p + e);
+    const float4 ee = *reinterpret_cast<const float4*>(ema + e);
+    *reinterpret_cast<float4*>(p + e) = ee;
+    *reinterpret_cast<float4*>(ema + e) = pp;
+    if (s.has_copy) {
+      const long long le = e - s.offset;
+      const float* na = &ee.x;
+      ushort4 w;
+      unsigned short* wa = &w.x;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float sc = 1.f;
+        if (s.scale_off >= 0) sc = scales[s.scale_off + (le + j) / s.row_len];
+        wa[j] = f2bf(na[j] * sc);
+      }
+      *reinterpret_cast<ushort4*>(wcopy + e) = w;
+    }
+  }
+  for (int i = (nv << 2) + threadIdx.x; i < c.len; i += kBlock) {
+    const long long e = base + i;
+    const float pj = p[e], ej = ema[e];
+    p[e] = ej; ema[e] = pj;
+    if (s.has_copy) {
+      float sc = 1.f;
+      if (s.scale_off >= 0) sc = scales[s.scale_off + (e - s.offset) / s.row_len];
+      wcopy[e] = f2bf(ej * sc);
+    }
   }
 }
 
@@ -230,9 +325,22 @@ MXR_API int mxr_chunk_struct_sizes(int* out) {
 MXR_API int mxr_adam_step(float* p, const float* g, float* m, float* v, void* wcopy, const float* scales,
                           const void* chunks, int nchunks, const void* segs, const float* grad_scale, float* hyper,
                           long long* iter, float b1, float b2, float eps, hipStream_t stream) {
-  adam_prologue<<<1, 1, 0, stream>>>(hyper, iter, b1, b2);
-  adam_kernel<<<nchunks, kBlock, 0, stream>>>(p, g, m, v, (bf16_t*)wcopy, scales, (const Chunk*)chunks,
-                                              (const Seg*)segs, grad_scale, hyper, b1, b2, eps);
+  adam_prologue<false><<<1, 1, 0, stream>>>(hyper, iter, b1, b2, 0.f, 0);
+  adam_kernel<false><<<nchunks, kBlock, 0, stream>>>(p, g, m, v, nullptr, (bf16_t*)wcopy, scales,
+                                                     (const Chunk*)chunks, (const Seg*)segs, grad_scale, hyper, b1, b2,
+                                                     eps);
+  return (int)hipGetLastError();
+}
+
+// The EMA form: `ema` is the fp32 average (shaped like p), D the decay cap, ema_start the step count at its seeding.
+MXR_API int mxr_adam_step_ema(float* p, const float* g, float* m, float* v, float* ema, void* wcopy,
+                              const float* scales, const void* chunks, int nchunks, const void* segs,
+                              const float* grad_scale, float* hyper, long long* iter, float b1, float b2, float eps,
+                              float D, long long ema_start, hipStream_t stream) {
+  if (!ema || nchunks <= 0) return (int)hipErrorInvalidValue;
+  adam_prologue<true><<<1, 1, 0, stream>>>(hyper, iter, b1, b2, D, ema_start);
+  adam_kernel<true><<<nchunks, kBlock, 0, stream>>>(p, g, m, v, ema, (bf16_t*)wcopy, scales, (const Chunk*)chunks,
+                                                    (const Seg*)segs, grad_scale, hyper, b1, b2, eps);
   return (int)hipGetLastError();
 }
 
@@ -240,16 +348,40 @@ MXR_API int mxr_adam_step(float* p, const float* g, float* m, float* v, void* wc
 MXR_API int mxr_sgd_step(float* p, const float* g, float* v, void* wcopy, const float* scales, const void* chunks,
                          int nchunks, const void* segs, const float* seg_wd, const float* grad_scale,
                          const float* hyper, long long* iter, int nesterov, hipStream_t stream) {
-#define MXR_SGD(N, D)                                                                                         \
-  sgd_kernel<N, D><<<nchunks, kBlock, 0, stream>>>(p, g, v, (bf16_t*)wcopy, scales, (const Chunk*)chunks,     \
-                                                   (const Seg*)segs, seg_wd, grad_scale, hyper, iter)
+#define MXR_SGD(N, D, E, EMA)                                                                                 \
+  sgd_kernel<N, D, E><<<nchunks, kBlock, 0, stream>>>(p, g, v, EMA, (bf16_t*)wcopy, scales,                   \
+                                                      (const Chunk*)chunks, (const Seg*)segs, seg_wd, grad_scale, \
+                                                      hyper, iter)
   if (nchunks <= 0) return (int)hipErrorInvalidValue;
   if (nesterov) {
-    if (seg_wd) MXR_SGD(true, true); else MXR_SGD(true, false);
+    if (seg_wd) MXR_SGD(true, true, false, nullptr); else MXR_SGD(true, false, false, nullptr);
   } else {
-    if (seg_wd) MXR_SGD(false, true); else MXR_SGD(false, false);
+    if (seg_wd) MXR_SGD(false, true, false, nullptr); else MXR_SGD(false, false, false, nullptr);
+  }
+  return (int)hipGetLastError();
+}
+
+// The EMA forms (as mxr_adam_step_ema); the prologue launch belongs to them alone.
+MXR_API int mxr_sgd_step_ema(float* p, const float* g, float* v, float* ema, void* wcopy, const float* scales,
+                             const void* chunks, int nchunks, const void* segs, const float* seg_wd,
+                             const float* grad_scale, float* hyper, long long* iter, int nesterov, float D,
+                             long long ema_start, hipStream_t stream) {
+  if (!ema || nchunks <= 0) return (int)hipErrorInvalidValue;
+  ema_prologue<<<1, 1, 0, stream>>>(hyper, iter, D, ema_start);
+  if (nesterov) {
+    if (seg_wd) MXR_SGD(true, true, true, ema); else MXR_SGD(true, false, true, ema);
+  } else {
+    if (seg_wd) MXR_SGD(false, true, true, ema); else MXR_SGD(false, false, true, ema);
   }
 #undef MXR_SGD
+  return (int)hipGetLastError();
+}
+
+// Exchange p and ema element by element and write the bf16 W*s compute copy of the new p: one pass, no temporary.
+MXR_API int mxr_swap_refresh(float* p, float* ema, void* wcopy, const float* scales, const void* chunks, int nchunks,
+                             const void* segs, hipStream_t stream) {
+  if (!p || !ema || nchunks <= 0) return (int)hipErrorInvalidValue;
+  swap_kernel<<<nchunks, kBlock, 0, stream>>>(p, ema, (bf16_t*)wcopy, scales, (const Chunk*)chunks, (const Seg*)segs);
   return (int)hipGetLastError();
 }
 
