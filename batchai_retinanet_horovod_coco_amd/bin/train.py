@@ -8,7 +8,7 @@ Same subcommands, flags, defaults and argument checks as ``/root/reference/train
 ``--no-evaluation``, ``--freeze-backbone``, ``--random-transform``, ``--image-min-side``,
 ``--image-max-side``), plus a ``synthetic`` dataset and MI355X options (``--dtype``, ``--clip-mode``,
 ``--bucket-mb``, ``--allreduce-dtype``, ``--workers``, ``--shard-data``, ``--checkpoint-format``,
-``--lr``, ``--clipnorm``, ``--optimizer``, ``--momentum``, ``--nesterov``, ``--weight-decay``, ``--ema-decay``, ``--weights-ema``, ``--warmup-epochs``, ``--seed``, ``--log-every``, ``--no-metric-average``, ``--log-all-ranks``,
+``--lr``, ``--clipnorm``, ``--optimizer``, ``--momentum``, ``--nesterov``, ``--weight-decay``, ``--ema-decay``, ``--weights-ema``, ``--regression-loss``, ``--regression-weight``, ``--warmup-epochs``, ``--seed``, ``--log-every``, ``--no-metric-average``, ``--log-all-ranks``,
 ``--metrics-jsonl``, ``--stop-on-nan``, ``--graph``, ``--graph-shapes``, ``--eval-batch-size``,
 ``--eval-pad-multiple``, ``--eval-workers``).
 
@@ -55,6 +55,7 @@ def check_args(parsed_args):
     if getattr(parsed_args, "graph_shapes", 1) < 1:
         raise SystemExit("--graph-shapes must be at least 1")
     resolve_optimizer(parsed_args)
+    resolve_regression_loss(parsed_args)
     if getattr(parsed_args, "warmup_epochs", 0) < 0:
         raise SystemExit("--warmup-epochs must be >= 0")
     if not 0.0 <= getattr(parsed_args, "ema_decay", 0.0) < 1.0:
@@ -91,6 +92,35 @@ def resolve_optimizer(parsed_args):
                                                                   stored))
     if parsed_args.weight_decay and parsed_args.optimizer == "adam":
         raise SystemExit("--weight-decay goes with --optimizer sgd; weight decay for adam is not implemented")
+    return parsed_args
+
+
+def resolve_regression_loss(parsed_args):
+    """``--regression-loss`` / ``--regression-weight`` when given, else what ``--snapshot`` stores, else smooth_l1 and
+    1.  The loss has no state, so a flag that differs from the snapshot wins, with a warning."""
+    if not hasattr(parsed_args, "regression_loss"):
+        return parsed_args
+    stored, stored_w = None, 1.0
+    if parsed_args.snapshot and os.path.exists(parsed_args.snapshot):
+        from ..io import checkpoint
+        stored = checkpoint.stored_regression_loss(parsed_args.snapshot)
+        stored_w = checkpoint.stored_regression_weight(parsed_args.snapshot)
+    choices = ("smooth_l1", "giou", "diou", "ciou")
+    if parsed_args.regression_loss is None:
+        parsed_args.regression_loss = stored if stored in choices else "smooth_l1"
+        if parsed_args.regression_weight is None and parsed_args.regression_loss == stored:
+            parsed_args.regression_weight = stored_w
+    elif stored is not None and stored != parsed_args.regression_loss:
+        warnings.warn("--regression-loss {} differs from --snapshot {}, which was trained with {}: training on with {}"
+                      .format(parsed_args.regression_loss, parsed_args.snapshot, stored, parsed_args.regression_loss))
+    elif parsed_args.regression_weight is None and stored == parsed_args.regression_loss:
+        parsed_args.regression_weight = stored_w
+    if parsed_args.regression_weight is None:
+        parsed_args.regression_weight = 1.0
+    if parsed_args.regression_weight <= 0:
+        raise SystemExit("--regression-weight must be positive")
+    if parsed_args.regression_loss == "smooth_l1" and parsed_args.regression_weight != 1.0:
+        raise SystemExit("--regression-weight goes with --regression-loss giou, diou or ciou; smooth_l1 has no weight")
     return parsed_args
 
 
@@ -205,6 +235,14 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--weights-ema", action="store_true",
                         help="With --weights FILE: load the averaged weights the file holds (an error if it has "
                              "none).")
+    parser.add_argument("--regression-loss", choices=["smooth_l1", "giou", "diou", "ciou"], default=None,
+                        help="Box regression loss.  smooth_l1 (default): the reference's, on the corner deltas.  giou, "
+                             "diou, ciou: an IoU loss of the decoded boxes over the positive anchors, loss and "
+                             "gradient in one fused kernel.  With --snapshot the loss stored in the file is used "
+                             "unless this flag is given; the flag wins (the loss has no state).")
+    parser.add_argument("--regression-weight", type=float, default=None, metavar="W",
+                        help="Weight of the IoU regression loss against the focal loss (default 1, or what --snapshot "
+                             "stores; not with smooth_l1).")
     parser.add_argument("--warmup-epochs", type=float, default=0, metavar="E",
                         help="Horovod's gradual warmup over the first E epochs, from lr / ranks up to --lr "
                              "(--lr is the rate after the warmup).  Default 0: off.")
@@ -472,6 +510,8 @@ def main(args=None):
                       compression=comp, bucket_bytes=int(args.bucket_mb * 2 ** 20) if args.bucket_mb else None,
                       device=dev, overlap=not args.no_overlap,
                       **(dict(ema_decay=args.ema_decay) if args.ema_decay > 0 else {}),
+                      **(dict(regression_loss=args.regression_loss, regression_weight=args.regression_weight)
+                         if args.regression_loss != "smooth_l1" else {}),
                       **(dict(optimizer="sgd", momentum=args.momentum, nesterov=args.nesterov,
                               weight_decay=args.weight_decay) if args.optimizer == "sgd" else {}))
     if args.snapshot is not None:

@@ -91,8 +91,7 @@ def _slots(optimizer) -> List[torch.Tensor]:
     return [st[k] for k in (("m", "v") if optimizer_class(optimizer) == "Adam" else ("velocity",))]
 
 
-def stored_optimizer_class(path: str) -> Optional[str]:
-    """The optimizer class a checkpoint was written with (None when it stores no training config)."""
+def _stored_training_config(path: str) -> Optional[Dict]:
     if path.endswith(".safetensors"):
         from safetensors import safe_open
         with safe_open(path, framework="pt") as f:
@@ -101,9 +100,28 @@ def stored_optimizer_class(path: str) -> Optional[str]:
     else:
         raw = hdf5.File(path, "r").attrs.get("training_config")
         raw = bytes(raw).decode() if raw is not None else None
-    if not raw:
+    return json.loads(raw) if raw else None
+
+
+def stored_optimizer_class(path: str) -> Optional[str]:
+    """The optimizer class a checkpoint was written with (None when it stores no training config)."""
+    cfg = _stored_training_config(path)
+    if cfg is None:
         return None
-    return json.loads(raw).get("optimizer_config", {}).get("class_name")
+    return cfg.get("optimizer_config", {}).get("class_name")
+
+
+def stored_regression_loss(path: str) -> Optional[str]:
+    """The regression loss a checkpoint was trained with -- ``smooth_l1``, ``giou``, ``diou`` or ``ciou`` -- (None
+    when it stores no training config)."""
+    cfg = _stored_training_config(path)
+    name = (cfg or {}).get("loss", {}).get("regression")
+    return name.lstrip("_") if name else None
+
+
+def stored_regression_weight(path: str) -> float:
+    """The weight of the regression loss a checkpoint was trained with (1 unless the file says otherwise)."""
+    return float((_stored_training_config(path) or {}).get("regression_weight", 1.0))
 
 
 def _class_mismatch(path: str, optimizer) -> bool:
@@ -117,9 +135,13 @@ def _class_mismatch(path: str, optimizer) -> bool:
 
 def training_config(optimizer) -> Dict:
     cfg = optimizer.get_config() if optimizer is not None else {}
-    return {"optimizer_config": {"class_name": optimizer_class(optimizer) or "Adam", "config": cfg},
-            "loss": {"regression": "_smooth_l1", "classification": "_focal"},
-            "metrics": [], "sample_weight_mode": None, "loss_weights": None}
+    out = {"optimizer_config": {"class_name": optimizer_class(optimizer) or "Adam", "config": cfg},
+           # the Trainer marks its optimizer with an IoU regression loss; without one it is the reference's
+           "loss": {"regression": "_" + getattr(optimizer, "regression_loss", "smooth_l1"), "classification": "_focal"},
+           "metrics": [], "sample_weight_mode": None, "loss_weights": None}
+    if getattr(optimizer, "regression_weight", 1.0) != 1.0:
+        out["regression_weight"] = float(optimizer.regression_weight)
+    return out
 
 
 _TO_KERAS = {"kernel": (1, 2, 3, 0), "oihw": (2, 3, 1, 0), "dw": (2, 3, 0, 1)}

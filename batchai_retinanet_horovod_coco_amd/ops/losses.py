@@ -12,10 +12,13 @@ Behavioural spec: keras-retinanet ``losses.focal(alpha=0.25, gamma=2.0)`` and
   kernel (``csrc/kernels/losses.hip``) that writes the loss partial sums *and* dlogits in
   a single pass over the 16M-logit/image classification tensor; the torch fallback is
   used on the CPU.
+* ``iou_loss`` (GIoU / DIoU / CIoU of the decoded boxes, ``Trainer(regression_loss=...)``) takes smooth-L1's place
+  on request: the torch expression here is the CPU path and the oracle of ``iou_loss_kernel``.
 """
 from __future__ import annotations
 
 import math
+from typing import Optional
 
 import torch
 
@@ -88,6 +91,67 @@ def _smooth_l1_torch(reg, reg_t, state, sigma):
     l = torch.where(d < 1.0 / s2, 0.5 * s2 * d * d, d - 0.5 / s2)
     l = (l * pos[..., None].to(l.dtype)).sum()
     return l / torch.clamp(pos.sum().to(l.dtype), min=1.0)
+
+
+IOU_KINDS = ("giou", "diou", "ciou")
+IOU_EPS = 1e-7
+
+
+def iou_loss_rows(anchors: torch.Tensor, pred: torch.Tensor, target: torch.Tensor, kind: str,
+                  alpha: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The per-row GIoU / DIoU / CIoU loss of predicted against target deltas, (N, 4) each with their anchors
+    (N, 4), in the dtype of the inputs.  Both boxes are ``bbox_transform_inv`` of their deltas; the predicted one
+    has its corners ordered (a linear decode can flip).  ``alpha``: CIoU's trade-off weight per row instead of the
+    one these boxes give (the backward holds it fixed; so does a check of the gradient against differences)."""
+    from .boxes import bbox_transform_inv
+    eps = IOU_EPS
+    gx1, gy1, gx2, gy2 = bbox_transform_inv(anchors, target).unbind(-1)
+    qx1, qy1, qx2, qy2 = bbox_transform_inv(anchors, pred).unbind(-1)
+    px1, px2 = torch.minimum(qx1, qx2), torch.maximum(qx1, qx2)
+    py1, py2 = torch.minimum(qy1, qy2), torch.maximum(qy1, qy2)
+    iw = (torch.minimum(px2, gx2) - torch.maximum(px1, gx1)).clamp_min(0)
+    ih = (torch.minimum(py2, gy2) - torch.maximum(py1, gy1)).clamp_min(0)
+    inter = iw * ih
+    union = (px2 - px1) * (py2 - py1) + (gx2 - gx1) * (gy2 - gy1) - inter + eps
+    iou = inter / union
+    cw = torch.maximum(px2, gx2) - torch.minimum(px1, gx1)
+    ch = torch.maximum(py2, gy2) - torch.minimum(py1, gy1)
+    if kind == "giou":
+        c = cw * ch + eps
+        return 1 - iou + (c - union) / c
+    c2 = cw * cw + ch * ch + eps
+    rho2 = ((px1 + px2 - gx1 - gx2) ** 2 + (py1 + py2 - gy1 - gy2) ** 2) / 4
+    diou = 1 - iou + rho2 / c2
+    if kind == "diou":
+        return diou
+    if kind != "ciou":
+        raise ValueError("kind must be one of {}, got {!r}".format(IOU_KINDS, kind))
+    v = 4 / math.pi ** 2 * (torch.atan((gx2 - gx1) / (gy2 - gy1 + eps)) - torch.atan((px2 - px1) / (py2 - py1 + eps))) ** 2
+    if alpha is None:
+        alpha = (v / (1 - iou + v + eps)).detach()    # a constant in the backward, as in the paper
+    return diou + alpha * v
+
+
+def _iou_loss_torch(reg, reg_t, state, anchors, kind, weight):
+    A = anchors.shape[0]
+    pos = (state == 1).reshape(-1, A)
+    an = anchors.float()[None].expand(pos.shape[0], A, 4)[pos]
+    l = iou_loss_rows(an, reg.float().reshape(-1, A, 4)[pos], reg_t.float().reshape(-1, A, 4)[pos], kind).sum()
+    return weight * l / torch.clamp(pos.sum().to(l.dtype), min=1.0)
+
+
+def iou_loss(reg: torch.Tensor, reg_t: torch.Tensor, state: torch.Tensor, anchors: torch.Tensor, kind: str,
+             weight: float = 1.0, backend: str = "auto") -> torch.Tensor:
+    """``weight`` x the GIoU / DIoU / CIoU loss of the decoded boxes over positive anchors; reg / reg_t (B, A, 4)
+    deltas, anchors (A, 4)."""
+    from . import native
+    if kind not in IOU_KINDS:
+        raise ValueError("kind must be one of {}, got {!r}".format(IOU_KINDS, kind))
+    if backend == "auto":
+        backend = "hip" if (reg.is_cuda and native.available()) else "torch"
+    if backend == "hip":
+        return native.IoULossFn.apply(reg, reg_t, state, anchors, kind, weight)
+    return _iou_loss_torch(reg, reg_t, state, anchors, kind, weight)
 
 
 def focal_loss(logits: torch.Tensor, state: torch.Tensor, label: torch.Tensor,

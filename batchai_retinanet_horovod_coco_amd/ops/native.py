@@ -45,6 +45,8 @@ _SIGS = {
     "mxr_focal_fwd_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_float, c_float, c_float, c_float,
                           c_int, c_int, c_int, c_vp],
     "mxr_smooth_l1_fwd_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_float, c_int, c_int, c_int, c_vp],
+    "mxr_iou_loss_fwd_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_int, c_float, c_int, c_int,
+                             c_int, c_vp],
     "mxr_loss_grid": [],
     "mxr_anchor_targets": [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_float, c_float,
                            c_float, c_vp],
@@ -339,6 +341,40 @@ def smooth_l1_fwd_bwd(reg, reg_t, state, npos=None, sigma=3.0, grad_out=None, gr
     return out.reshape(()), grad
 
 
+IOU_KINDS = {"giou": 0, "diou": 1, "ciou": 2}
+
+
+def iou_loss_fwd_bwd(reg, reg_t, anchors, state, npos=None, kind="giou", weight=1.0, grad_out=None, group=0):
+    """GIoU / DIoU / CIoU of the decoded boxes over the positive anchors (``iou_loss_kernel``): returns
+    (loss 0-d f32, dreg like reg), both times ``weight``.  ``anchors`` (A, 4) f32 are those of one image; row r of
+    reg uses anchor r % A.  ``grad_out`` / ``group``: as in :func:`smooth_l1_fwd_bwd`."""
+    if kind not in IOU_KINDS:
+        raise ValueError("iou_loss_fwd_bwd: kind must be one of {}, got {!r}".format(sorted(IOU_KINDS), kind))
+    reg = reg.contiguous()
+    rows = reg.numel() // 4
+    A = anchors.shape[0]
+    if not (anchors.dim() == 2 and anchors.shape[1] == 4 and anchors.dtype == torch.float32 and A > 0
+            and rows % A == 0 and reg_t.numel() == rows * 4 and state.numel() == rows and state.dtype == torch.int8):
+        raise ValueError("iou_loss_fwd_bwd: reg / reg_t (rows, 4), state (rows,) int8 and anchors (A, 4) f32 with "
+                         "rows a multiple of A expected")
+    npos = _npos(state, npos)
+    ld = 0
+    if grad_out is not None:
+        ld = grad_out.shape[-1]
+        if not (grad_out.is_contiguous() and grad_out.dtype == reg.dtype and group > 0
+                and grad_out.numel() == rows // group * ld):
+            raise ValueError("iou_loss_fwd_bwd: grad_out does not match the padded layout")
+        grad = grad_out
+    else:
+        grad = torch.empty_like(reg)
+    part = torch.empty(LOSS_GRID, dtype=torch.float32, device=reg.device)
+    out = torch.empty(1, dtype=torch.float32, device=reg.device)
+    _chk(lib().mxr_iou_loss_fwd_bwd(_p(reg), _p(reg_t.float().contiguous()), _p(anchors.contiguous()),
+                                    _p(state.contiguous()), _p(npos), _p(grad), _p(part), _p(out), rows, A,
+                                    IOU_KINDS[kind], weight, _dt(reg), int(group) if ld else 0, ld, _s()), "iou_loss")
+    return out.reshape(()), grad
+
+
 class FocalLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, state, label, alpha, gamma, npos=None):
@@ -363,6 +399,19 @@ class SmoothL1Fn(torch.autograd.Function):
     def backward(ctx, g):
         (grad,) = ctx.saved_tensors
         return grad * g.to(grad.dtype), None, None, None, None
+
+
+class IoULossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, reg, reg_t, state, anchors, kind, weight, npos=None):
+        loss, grad = iou_loss_fwd_bwd(reg, reg_t, anchors, state, npos, kind, weight)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g.to(grad.dtype), None, None, None, None, None, None
 
 
 # =========================================================================================

@@ -54,8 +54,15 @@ class Trainer:
                  clip_mode: str = "local", compression=None, bucket_bytes: Optional[int] = None,
                  device: Optional[torch.device] = None, overlap: bool = True, target_backend: str = "auto",
                  optimizer: str = "adam", momentum: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0,
-                 ema_decay: float = 0.0):
+                 ema_decay: float = 0.0, regression_loss: str = "smooth_l1", regression_weight: float = 1.0):
         from ..parallel.collectives import Compression
+        if regression_loss != "smooth_l1" and regression_loss not in losses.IOU_KINDS:
+            raise ValueError("regression_loss must be 'smooth_l1' or one of {}, got {!r}".format(
+                losses.IOU_KINDS, regression_loss))
+        if regression_loss == "smooth_l1" and regression_weight != 1.0:
+            raise ValueError("regression_weight goes with the IoU regression losses; smooth_l1 has no weight")
+        self.regression_loss = regression_loss
+        self.regression_weight = float(regression_weight)
         self.device = device or (runtime.device() if runtime.is_initialized() else torch.device("cpu"))
         self.model = model.to(self.device)
         self.compute_dtype = compute_dtype
@@ -71,6 +78,10 @@ class Trainer:
             raise ValueError("optimizer must be 'adam' or 'sgd', got {!r}".format(optimizer))
         self.optimizer = DistributedOptimizer(self.base_optimizer, compression=compression or Compression.none,
                                               clip_mode=clip_mode, bucket_bytes=bucket_bytes, overlap=overlap)
+        if regression_loss != "smooth_l1":
+            # what a snapshot records about the loss (io.checkpoint.training_config reads it off the optimizer)
+            self.base_optimizer.regression_loss = regression_loss
+            self.base_optimizer.regression_weight = self.regression_weight
         self.anchors = anchor_ops.AnchorCache()
         self.num_classes = model.num_classes
         self.target_backend = target_backend
@@ -128,7 +139,28 @@ class Trainer:
                 if req is not None:
                     self.model.focal_request = None
         with _range("backward"):
-            return self._losses_backward(out, reg_t, state, label, npos)
+            return self._losses_backward(out, reg_t, state, label, npos, self._loss_anchors(images))
+
+    def _loss_anchors(self, images):
+        """The anchors of the batch's padded shape for the IoU regression losses (the cache's persistent tensor: a
+        captured step keeps a valid pointer); None with smooth-L1, which needs none."""
+        if self.regression_loss == "smooth_l1":
+            return None
+        return self.anchors.get((int(images.shape[1]), int(images.shape[2])), self.device, self.shapes_callback)
+
+    def _regression_fwd_bwd(self, reg, reg_t, state, npos, anchors, **pad):
+        """The fused regression loss kernel of this trainer: (loss, d loss / d reg)."""
+        from ..ops import native
+        if self.regression_loss == "smooth_l1":
+            return native.smooth_l1_fwd_bwd(reg, reg_t, state, npos, **pad)
+        return native.iou_loss_fwd_bwd(reg, reg_t, anchors, state, npos, kind=self.regression_loss,
+                                       weight=self.regression_weight, **pad)
+
+    def _regression_torch(self, reg, reg_t, state, anchors):
+        if self.regression_loss == "smooth_l1":
+            return losses.smooth_l1_loss(reg, reg_t, state, backend="torch")
+        return losses.iou_loss(reg, reg_t, state, anchors, self.regression_loss, self.regression_weight,
+                               backend="torch")
 
     def _focal_request(self, state, label, npos):
         """This step's targets for the classification final's fused focal loss (bf16 HIP heads with the padded
@@ -144,7 +176,7 @@ class Trainer:
         self.model.focal_request = self._focal_req
         return self._focal_req
 
-    def _losses_backward(self, out, reg_t, state, label, npos):
+    def _losses_backward(self, out, reg_t, state, label, npos, anchors=None):
         if self._fused_losses():
             # fused loss kernels emit d(loss)/d(outputs) directly; backprop from the outputs
             from ..ops import native
@@ -153,15 +185,15 @@ class Trainer:
             rsink = getattr(self.model, "reg_pad_sink", None)
             if rsink is not None and _PAD_FOCAL and reg.dtype == torch.bfloat16 and reg.shape[1] % A == 0 and \
                     (4 * A) % 64:
-                # smooth-L1 writes d(loss)/d(regression) into the final layer's 64-padded rows (36 -> 64);
+                # the loss kernel writes d(loss)/d(regression) into the final layer's 64-padded rows (36 -> 64);
                 # the layer's data / weight / bias gradients then read them as is (no pad, cast or slice)
                 key = (reg.shape[0], reg.shape[1] // A, (4 * A + 63) // 64 * 64, reg.device)
                 buf = self._reg_pad_buf.get(key, lambda: torch.zeros(key[:3], dtype=reg.dtype, device=reg.device))
-                reg_loss, dpad = native.smooth_l1_fwd_bwd(reg, reg_t, state, npos, grad_out=buf, group=A)
+                reg_loss, dpad = self._regression_fwd_bwd(reg, reg_t, state, npos, anchors, grad_out=buf, group=A)
                 rsink["dy"] = dpad
                 dreg = torch.zeros((), dtype=reg.dtype, device=reg.device).expand(reg.shape)
             else:
-                reg_loss, dreg = native.smooth_l1_fwd_bwd(reg, reg_t, state, npos)
+                reg_loss, dreg = self._regression_fwd_bwd(reg, reg_t, state, npos, anchors)
             cls = out["classification"]
             sink = getattr(self.model, "cls_pad_sink", None)
             cp = (A * cls.shape[-1] + 63) // 64 * 64
@@ -185,7 +217,7 @@ class Trainer:
                 cls_loss, dcls = native.focal_fwd_bwd(cls, state, label, npos)
             torch.autograd.backward([reg, cls], [dreg, dcls])
         else:
-            reg_loss = losses.smooth_l1_loss(out["regression"], reg_t, state, backend="torch")
+            reg_loss = self._regression_torch(out["regression"], reg_t, state, anchors)
             cls_loss = losses.focal_loss(out["classification"], state, label, backend="torch")
             (reg_loss + cls_loss).backward()
         return reg_loss.detach(), cls_loss.detach()
@@ -195,7 +227,7 @@ class Trainer:
         with torch.no_grad():
             state, label, reg_t, npos = self.compute_targets(images, gt, gt_count, image_hw)
             out = self.model(images.to(self.compute_dtype))
-            reg_loss = losses.smooth_l1_loss(out["regression"], reg_t, state, backend="torch")
+            reg_loss = self._regression_torch(out["regression"], reg_t, state, self._loss_anchors(images))
             cls_loss = losses.focal_loss(out["classification"], state, label, backend="torch")
         return reg_loss, cls_loss
 

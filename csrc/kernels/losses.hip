@@ -1,4 +1,5 @@
-// Fused sigmoid-focal and smooth-L1 losses: loss partial sums AND input gradients in one pass.
+// Fused sigmoid-focal and smooth-L1 losses: loss partial sums AND input gradients in one pass.  (And the IoU
+// regression losses that --regression-loss puts in smooth-L1's place: iou_loss_kernel below.)
 //
 // Spec: keras-retinanet losses.focal(alpha=0.25, gamma=2) / smooth_l1(sigma=3) compiled at
 // /root/reference/train.py:99-102.  Keras evaluates the focal weight on the
@@ -281,7 +282,157 @@ __global__ __launch_bounds__(kBlock) void smooth_l1_kernel(const T* __restrict__
   if (threadIdx.x == 0) partials[blockIdx.x] = bs;
 }
 
+// IoU regression losses over positive anchors: GIoU (Rezatofighi et al. 2019), DIoU / CIoU (Zheng et al. 2020).
+// pred / dpred: [rows, 4] (T) corner deltas, target: [rows, 4] f32 deltas, anchors: [A, 4] f32 (x1, y1, x2, y2);
+// row r belongs to anchor r % A.  Both boxes are the project's bbox_transform_inv (mean 0, std kBoxStd) of their
+// deltas; the predicted one has its corners ordered (the decode is linear, a prediction can flip) and the
+// gradient follows every selection: the ordering, pred corner vs target corner, the max(0, .) of the
+// intersection.  It comes out in delta units (through std * anchor side) and already / max(1, npos) * weight.
+// A row reads its prediction, target and anchor only when it is positive (~1 % of the rows), so the pass is the
+// state read plus the gradient write, as in smooth_l1_kernel.
+// The boxes are held relative to the anchor's top-left corner: the loss does not change under a translation, and
+// coordinates of the anchor's own size keep the fp32 differences (widths, overlaps) a few ulp from exact where
+// image coordinates of ~1000 px would cost them 2-3 digits.
+enum { kGIoU = 0, kDIoU = 1, kCIoU = 2 };
+constexpr float kBoxStd = 0.2f;
+constexpr float kIoUEps = 1e-7f;
+
+template <> struct Vec<bf16_t, 4> { typedef uint2 type; };
+
+template <typename T, int KIND>
+__global__ __launch_bounds__(kBlock) void iou_loss_kernel(const T* __restrict__ pred, const float* __restrict__ target,
+                                                          const float* __restrict__ anchors,
+                                                          const int8_t* __restrict__ state, const int* __restrict__ npos,
+                                                          T* __restrict__ dpred, float* __restrict__ partials,
+                                                          long long rows, int A, float weight, int grp, int ld,
+                                                          bool vec) {
+  __shared__ float red[16];
+  typedef typename Vec<T, 4>::type VT;
+  const float gs = weight / fmaxf(1.0f, (float)(*npos));
+  const bool small = rows < 0x7fffffffLL;   // 32-bit division (64-bit integer division is emulated on CDNA)
+  float acc = 0.f;
+  for (long long r = blockIdx.x * (long long)kBlock + threadIdx.x; r < rows; r += (long long)gridDim.x * kBlock) {
+    T g[4];
+    if (state[r] == 1) {
+      const int a = small ? (int)r % A : (int)(r % A);
+      const float4 an = reinterpret_cast<const float4*>(anchors)[a];
+      const float4 t = reinterpret_cast<const float4*>(target)[r];
+      T ps[4];
+      if (vec) {
+        *reinterpret_cast<VT*>(ps) = reinterpret_cast<const VT*>(pred)[r];
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ps[j] = pred[r * 4 + j];
+      }
+      const float aw = an.z - an.x, ah = an.w - an.y;
+      const float sw = kBoxStd * aw, sh = kBoxStd * ah;
+      const float gx1 = sw * t.x, gy1 = sh * t.y, gx2 = aw + sw * t.z, gy2 = ah + sh * t.w;
+      const float qx1 = sw * Cvt<T>::to_f(ps[0]), qy1 = sh * Cvt<T>::to_f(ps[1]);
+      const float qx2 = aw + sw * Cvt<T>::to_f(ps[2]), qy2 = ah + sh * Cvt<T>::to_f(ps[3]);
+      const bool fx = qx1 > qx2, fy = qy1 > qy2;      // flipped: the gradients of (x1, x2) / (y1, y2) change places
+      const float px1 = fx ? qx2 : qx1, px2 = fx ? qx1 : qx2, py1 = fy ? qy2 : qy1, py2 = fy ? qy1 : qy2;
+      const float pw = px2 - px1, ph = py2 - py1, gw = gx2 - gx1, gh = gy2 - gy1;
+      const float iwr = fminf(px2, gx2) - fmaxf(px1, gx1), ihr = fminf(py2, gy2) - fmaxf(py1, gy1);
+      const float iw = fmaxf(iwr, 0.f), ih = fmaxf(ihr, 0.f);
+      const float I = iw * ih;
+      const float U = pw * ph + gw * gh - I + kIoUEps;
+      const float rU = 1.0f / U;
+      const float iou = I * rU;
+      const float cw = fmaxf(px2, gx2) - fminf(px1, gx1), ch = fmaxf(py2, gy2) - fminf(py1, gy1);
+      // which corner each selection took: l* -- the prediction's corner bounds the enclosing box, i* -- the
+      // intersection (and the intersection is not clamped away)
+      const bool lx1 = px1 < gx1, lx2 = px2 > gx2, ly1 = py1 < gy1, ly2 = py2 > gy2;
+      const bool ix1 = iwr > 0.f && px1 > gx1, ix2 = iwr > 0.f && px2 < gx2;
+      const bool iy1 = ihr > 0.f && py1 > gy1, iy2 = ihr > 0.f && py2 < gy2;
+      // d / d(px1, px2, py1, py2) of I and of U
+      const float dI[4] = {ix1 ? -ih : 0.f, ix2 ? ih : 0.f, iy1 ? -iw : 0.f, iy2 ? iw : 0.f};
+      const float dU[4] = {-ph - dI[0], ph - dI[1], -pw - dI[2], pw - dI[3]};
+      float G[4];     // d L / d(px1, px2, py1, py2)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) G[j] = (iou * dU[j] - dI[j]) * rU;     // -d IoU
+      float L;
+      if constexpr (KIND == kGIoU) {
+        const float C = cw * ch + kIoUEps;
+        const float rC = 1.0f / C;
+        const float uc = U * rC;
+        L = 1.0f - iou + (C - U) * rC;
+        const float dC[4] = {lx1 ? -ch : 0.f, lx2 ? ch : 0.f, ly1 ? -cw : 0.f, ly2 ? cw : 0.f};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) G[j] -= (dU[j] - uc * dC[j]) * rC;   // -d (U / C)
+      } else {
+        const float c2 = cw * cw + ch * ch + kIoUEps;
+        const float rc2 = 1.0f / c2;
+        const float sx = (px1 + px2) - (gx1 + gx2), sy = (py1 + py2) - (gy1 + gy2);
+        const float rr = 0.25f * (sx * sx + sy * sy) * rc2;
+        L = 1.0f - iou + rr;
+        const float dc2[4] = {lx1 ? -2.f * cw : 0.f, lx2 ? 2.f * cw : 0.f, ly1 ? -2.f * ch : 0.f, ly2 ? 2.f * ch : 0.f};
+        const float drho2[4] = {0.5f * sx, 0.5f * sx, 0.5f * sy, 0.5f * sy};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) G[j] += (drho2[j] - rr * dc2[j]) * rc2;
+        if constexpr (KIND == kCIoU) {
+          const float php = ph + kIoUEps, ghp = gh + kIoUEps;
+          const float at = atanf(gw / ghp) - atanf(pw / php);
+          const float v = 0.40528473456935108578f * at * at;             // 4 / pi^2
+          const float alpha = v / (1.0f - iou + v + kIoUEps);            // a constant in the backward
+          L += alpha * v;
+          const float k = alpha * 0.81056946913870217155f * at / (php * php + pw * pw);   // 8 / pi^2
+          G[0] += k * php;     // d v / d pw = -k php / alpha, d pw / d px1 = -1
+          G[1] -= k * php;
+          G[2] -= k * pw;      // d v / d ph = k pw / alpha
+          G[3] += k * pw;
+        }
+      }
+      acc += weight * L;
+      const float kx = gs * sw, ky = gs * sh;
+      g[0] = Cvt<T>::from_f(kx * (fx ? G[1] : G[0]));
+      g[1] = Cvt<T>::from_f(ky * (fy ? G[3] : G[2]));
+      g[2] = Cvt<T>::from_f(kx * (fx ? G[0] : G[1]));
+      g[3] = Cvt<T>::from_f(ky * (fy ? G[2] : G[3]));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) g[j] = Cvt<T>::from_f(0.f);
+    }
+    // grp / ld: the packed regression head's zero-padded [rows / grp][ld] gradient rows
+    long long o = r * 4;
+    if (ld > 0) {
+      if (small) {
+        const int q = (int)r / grp;
+        o = q * (long long)ld + ((int)r - q * grp) * 4;
+      } else {
+        o = (r / grp) * ld + (r % grp) * 4;
+      }
+    }
+    if (vec) {
+      *reinterpret_cast<VT*>(dpred + o) = *reinterpret_cast<const VT*>(g);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) dpred[o + j] = g[j];
+    }
+  }
+  const float bs = block_sum(acc, red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = bs;
+}
+
 constexpr int kLossGrid = 2048;
+
+template <typename T>
+void iou_loss_launch(int kind, const void* pred, const float* target, const float* anchors, const int8_t* state,
+                     const int* npos, void* dpred, float* partials, long long rows, int A, float weight, int grp,
+                     int ld, hipStream_t stream) {
+  // one 8-B (bf16) / 16-B (f32) access per row where every row starts on such a boundary
+  const bool vec = ld % 4 == 0 && ((uintptr_t)pred | (uintptr_t)dpred) % (4 * sizeof(T)) == 0;
+  const T* p = (const T*)pred;
+  T* d = (T*)dpred;
+  if (kind == kGIoU)
+    iou_loss_kernel<T, kGIoU><<<kLossGrid, kBlock, 0, stream>>>(p, target, anchors, state, npos, d, partials, rows, A,
+                                                                weight, grp, ld, vec);
+  else if (kind == kDIoU)
+    iou_loss_kernel<T, kDIoU><<<kLossGrid, kBlock, 0, stream>>>(p, target, anchors, state, npos, d, partials, rows, A,
+                                                                weight, grp, ld, vec);
+  else
+    iou_loss_kernel<T, kCIoU><<<kLossGrid, kBlock, 0, stream>>>(p, target, anchors, state, npos, d, partials, rows, A,
+                                                                weight, grp, ld, vec);
+}
 
 }  // namespace
 
@@ -338,6 +489,21 @@ MXR_API int mxr_smooth_l1_fwd_bwd(const void* pred, const float* target, const i
   else
     smooth_l1_kernel<float><<<kLossGrid, kBlock, 0, stream>>>((const float*)pred, target, state, npos,
                                                               (float*)dpred, partials, rows, s2, grp, ld);
+  finalize_kernel<<<1, 256, 0, stream>>>(partials, kLossGrid, npos, out);
+  return (int)hipGetLastError();
+}
+
+// kind: 0 = GIoU, 1 = DIoU, 2 = CIoU.  anchors: [A, 4] f32; rows must be a multiple of A.  Everything else as in
+// mxr_smooth_l1_fwd_bwd.
+MXR_API int mxr_iou_loss_fwd_bwd(const void* pred, const float* target, const float* anchors, const int8_t* state,
+                                 const int* npos, void* dpred, float* partials, float* out, long long rows, int A,
+                                 int kind, float weight, int dtype, int grp, int ld, hipStream_t stream) {
+  if (ld > 0 && (grp <= 0 || 4LL * grp > ld || rows % grp)) return -1;
+  if (A <= 0 || rows % A || kind < kGIoU || kind > kCIoU) return -1;
+  if (dtype == 1)
+    iou_loss_launch<bf16_t>(kind, pred, target, anchors, state, npos, dpred, partials, rows, A, weight, grp, ld, stream);
+  else
+    iou_loss_launch<float>(kind, pred, target, anchors, state, npos, dpred, partials, rows, A, weight, grp, ld, stream);
   finalize_kernel<<<1, 256, 0, stream>>>(partials, kLossGrid, npos, out);
   return (int)hipGetLastError();
 }
