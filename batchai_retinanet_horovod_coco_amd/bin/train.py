@@ -56,6 +56,7 @@ def check_args(parsed_args):
         raise SystemExit("--graph-shapes must be at least 1")
     resolve_optimizer(parsed_args)
     resolve_regression_loss(parsed_args)
+    resolve_assigner(parsed_args)
     if getattr(parsed_args, "warmup_epochs", 0) < 0:
         raise SystemExit("--warmup-epochs must be >= 0")
     if not 0.0 <= getattr(parsed_args, "ema_decay", 0.0) < 1.0:
@@ -121,6 +122,30 @@ def resolve_regression_loss(parsed_args):
         raise SystemExit("--regression-weight must be positive")
     if parsed_args.regression_loss == "smooth_l1" and parsed_args.regression_weight != 1.0:
         raise SystemExit("--regression-weight goes with --regression-loss giou, diou or ciou; smooth_l1 has no weight")
+    return parsed_args
+
+
+def resolve_assigner(parsed_args):
+    """``--assigner`` / ``--atss-topk`` when given, else what ``--snapshot`` stores, else iou and 9.  The assignment
+    has no state, so a flag that differs from the snapshot wins, with a warning."""
+    if not hasattr(parsed_args, "assigner"):
+        return parsed_args
+    stored, stored_k = None, 9
+    if parsed_args.snapshot and os.path.exists(parsed_args.snapshot):
+        from ..io import checkpoint
+        stored = checkpoint.stored_assigner(parsed_args.snapshot)
+        stored_k = checkpoint.stored_atss_topk(parsed_args.snapshot)
+    if parsed_args.assigner is None:
+        parsed_args.assigner = stored if stored in ("iou", "atss") else "iou"
+    elif stored is not None and stored != parsed_args.assigner:
+        warnings.warn("--assigner {} differs from --snapshot {}, which was trained with {}: training on with {}"
+                      .format(parsed_args.assigner, parsed_args.snapshot, stored, parsed_args.assigner))
+    if parsed_args.atss_topk is not None and parsed_args.assigner != "atss":
+        raise SystemExit("--atss-topk goes with --assigner atss; the fixed-threshold rule has no top-k")
+    if parsed_args.atss_topk is None:
+        parsed_args.atss_topk = stored_k if (parsed_args.assigner == "atss" and stored == "atss") else 9
+    if not 1 <= parsed_args.atss_topk <= 16:
+        raise SystemExit("--atss-topk must be in 1..16")
     return parsed_args
 
 
@@ -243,6 +268,15 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--regression-weight", type=float, default=None, metavar="W",
                         help="Weight of the IoU regression loss against the focal loss (default 1, or what --snapshot "
                              "stores; not with smooth_l1).")
+    parser.add_argument("--assigner", choices=["iou", "atss"], default=None,
+                        help="Anchor target assignment.  iou (default): the reference's fixed thresholds (IoU >= 0.5 "
+                             "positive, 0.4-0.5 ignored).  atss: adaptive training sample selection -- every box takes "
+                             "its own threshold, mean + std of the IoUs of the anchors at its --atss-topk nearest "
+                             "locations per level -- on the device.  With --snapshot the assigner stored in the file "
+                             "is used unless this flag is given; the flag wins (the assigner has no state).")
+    parser.add_argument("--atss-topk", type=int, default=None, metavar="K",
+                        help="With --assigner atss: locations per pyramid level whose anchors are a box's candidates "
+                             "(1..16; default 9, or what --snapshot stores).")
     parser.add_argument("--warmup-epochs", type=float, default=0, metavar="E",
                         help="Horovod's gradual warmup over the first E epochs, from lr / ranks up to --lr "
                              "(--lr is the rate after the warmup).  Default 0: off.")
@@ -512,6 +546,7 @@ def main(args=None):
                       **(dict(ema_decay=args.ema_decay) if args.ema_decay > 0 else {}),
                       **(dict(regression_loss=args.regression_loss, regression_weight=args.regression_weight)
                          if args.regression_loss != "smooth_l1" else {}),
+                      **(dict(assigner="atss", atss_topk=args.atss_topk) if args.assigner == "atss" else {}),
                       **(dict(optimizer="sgd", momentum=args.momentum, nesterov=args.nesterov,
                               weight_decay=args.weight_decay) if args.optimizer == "sgd" else {}))
     if args.snapshot is not None:

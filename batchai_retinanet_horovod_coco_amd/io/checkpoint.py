@@ -124,6 +124,18 @@ def stored_regression_weight(path: str) -> float:
     return float((_stored_training_config(path) or {}).get("regression_weight", 1.0))
 
 
+def stored_assigner(path: str) -> Optional[str]:
+    """The target assignment a checkpoint was trained with -- ``iou`` (the fixed thresholds) or ``atss`` -- (None when
+    it stores no training config)."""
+    cfg = _stored_training_config(path)
+    return None if cfg is None else cfg.get("assigner", "iou")
+
+
+def stored_atss_topk(path: str) -> int:
+    """The top-k of the ATSS assignment a checkpoint was trained with (9 unless the file says otherwise)."""
+    return int((_stored_training_config(path) or {}).get("atss_topk", 9))
+
+
 def _class_mismatch(path: str, optimizer) -> bool:
     stored, live = stored_optimizer_class(path), optimizer_class(optimizer)
     if stored is not None and stored != live:
@@ -141,6 +153,11 @@ def training_config(optimizer) -> Dict:
            "metrics": [], "sample_weight_mode": None, "loss_weights": None}
     if getattr(optimizer, "regression_weight", 1.0) != 1.0:
         out["regression_weight"] = float(optimizer.regression_weight)
+    if getattr(optimizer, "assigner", "iou") != "iou":
+        # likewise the target assignment: absent for the reference's fixed-threshold rule
+        out["assigner"] = optimizer.assigner
+        if getattr(optimizer, "atss_topk", 9) != 9:
+            out["atss_topk"] = int(optimizer.atss_topk)
     return out
 
 

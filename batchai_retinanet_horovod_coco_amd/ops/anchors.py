@@ -230,6 +230,17 @@ class AnchorCache:
     def centers(self, image_shape, device, shapes_callback=None) -> torch.Tensor:
         return self._entry(image_shape, device, shapes_callback)[1]
 
+    def levels(self, image_shape, device=None, shapes_callback=None) -> np.ndarray:
+        """The level table of the padded shape, (L, 4) int64 rows ``(first anchor index, h, w, stride)``: host
+        values (the ATSS kernels take them by value), the same for every device."""
+        key = (int(image_shape[0]), int(image_shape[1]), "levels")
+        t = self._cache.get(key)
+        if t is None:
+            t = level_table(image_shape, shapes_callback, anchor_params=self.p)
+            t.setflags(write=False)
+            self._cache[key] = t
+        return t
+
 
 def anchor_targets_torch(anchors: torch.Tensor, gt: torch.Tensor, gt_count: torch.Tensor,
                          mask_hw: torch.Tensor,
@@ -287,4 +298,244 @@ def anchor_targets_torch(anchors: torch.Tensor, gt: torch.Tensor, gt_count: torc
     reg = torch.stack([(mbox[..., 0] - ax1[None]) / aw, (mbox[..., 1] - ay1[None]) / ah,
                        (mbox[..., 2] - ax2[None]) / aw, (mbox[..., 3] - ay2[None]) / ah], -1)
     reg = (reg - BOX_MEAN) / BOX_STD
+    return state, label, reg
+
+
+# ----------------------------------------------------------------------------------------
+# ATSS (Zhang et al., CVPR 2020, Algorithm 1): per-box thresholds from the nearest anchors
+# ----------------------------------------------------------------------------------------
+ATSS_TOPK = 9
+ATSS_MAX_TOPK = 16
+ATSS_INSIDE_EPS = 0.01
+ATSS_WINDOW = 4         # half-size, in cells, of the window the HIP kernel scans around the box centre's cell
+
+
+def level_table(image_shape, shapes_callback=None, anchor_params: Optional[AnchorParameters] = None,
+                pyramid_levels=PYRAMID_LEVELS) -> np.ndarray:
+    """(L, 4) int64 rows ``(first anchor index, h, w, stride)`` of the padded shape, as ``anchors_for_shape`` lays the
+    levels out."""
+    p = anchor_params or AnchorParameters.default
+    shapes = (shapes_callback or guess_shapes)(image_shape[:2], pyramid_levels)
+    rows, first = [], 0
+    for idx in range(len(pyramid_levels)):
+        h, w = int(shapes[idx][0]), int(shapes[idx][1])
+        rows.append((first, h, w, int(p.strides[idx])))
+        first += h * w * p.num_anchors()
+    return np.asarray(rows, dtype=np.int64)
+
+
+def _check_topk(topk) -> int:
+    if int(topk) != topk or not 1 <= int(topk) <= ATSS_MAX_TOPK:
+        raise ValueError("topk must be an integer in 1..{}, got {!r}".format(ATSS_MAX_TOPK, topk))
+    return int(topk)
+
+
+def _check_levels(levels, A: int) -> Tuple[np.ndarray, int]:
+    """The level table as (L, 4) int64 and the anchors per location; a table that does not tile ``A`` is refused."""
+    lv = np.asarray(levels, dtype=np.int64).reshape(-1, 4)
+    locs = int((lv[:, 1] * lv[:, 2]).sum())
+    if lv.shape[0] == 0 or (lv[:, 1:] <= 0).any() or locs == 0 or A % locs:
+        raise ValueError("the level table {} does not add up to {} anchors".format(lv.tolist(), A))
+    A0 = A // locs
+    first = np.concatenate([[0], np.cumsum(lv[:, 1] * lv[:, 2] * A0)[:-1]])
+    if (lv[:, 0] != first).any():
+        raise ValueError("the level table {} does not add up to {} anchors".format(lv.tolist(), A))
+    return lv, A0
+
+
+def atss_window(h: int, w: int, stride: int, gcx: float, gcy: float, topk: int) -> Tuple[int, int, int, int]:
+    """The rectangle of locations ``(x0, x1, y0, y1)``, inclusive, in which the HIP kernel looks for the ``topk``
+    locations nearest to ``(gcx, gcy)``; this is that rule in Python.
+
+    The window is ATSS_WINDOW cells around the cell the point falls into, clipped to the grid.  A location outside it
+    is more than ATSS_WINDOW cells from that cell on one axis, and the point is at most half a cell from the cell's
+    centre on that axis (further only towards the grid's outside), so the location is at least ATSS_WINDOW + 0.5
+    strides away.  When the window holds ``topk`` locations closer than ATSS_WINDOW strides (half a stride of slack:
+    fp32 rounding is far below it), they beat every location outside it; otherwise the whole level is scanned."""
+    f32 = np.float32
+    R = ATSS_WINDOW
+    ix0 = min(max(int(math.floor(f32(gcx) / f32(stride))), 0), w - 1)
+    iy0 = min(max(int(math.floor(f32(gcy) / f32(stride))), 0), h - 1)
+    x0, x1, y0, y1 = max(ix0 - R, 0), min(ix0 + R, w - 1), max(iy0 - R, 0), min(iy0 + R, h - 1)
+    if x0 == 0 and y0 == 0 and x1 == w - 1 and y1 == h - 1:
+        return x0, x1, y0, y1
+    dx = (np.arange(x0, x1 + 1, dtype=f32) + f32(0.5)) * f32(stride) - f32(gcx)
+    dy = (np.arange(y0, y1 + 1, dtype=f32) + f32(0.5)) * f32(stride) - f32(gcy)
+    d2 = (dx * dx)[None, :] + (dy * dy)[:, None]
+    if int((d2 < f32(R * stride) * f32(R * stride)).sum()) >= min(topk, h * w):
+        return x0, x1, y0, y1
+    return 0, w - 1, 0, h - 1
+
+
+def _nearest_locations(h, w, stride, gcx, gcy, k, rect=None, dtype=np.float64) -> np.ndarray:
+    """The ``min(k, h * w)`` row-major location indices nearest to (gcx, gcy), ordered by (d2, index); brute force
+    over the level, or over ``rect`` = (x0, x1, y0, y1)."""
+    x0, x1, y0, y1 = rect or (0, w - 1, 0, h - 1)
+    t = dtype
+    dx = (np.arange(x0, x1 + 1).astype(t) + t(0.5)) * t(stride) - t(gcx)
+    dy = (np.arange(y0, y1 + 1).astype(t) + t(0.5)) * t(stride) - t(gcy)
+    d2 = ((dx * dx)[None, :] + (dy * dy)[:, None]).ravel()
+    idx = (np.arange(y0, y1 + 1)[:, None] * w + np.arange(x0, x1 + 1)[None, :]).ravel()
+    order = np.lexsort((idx, d2))
+    return idx[order[:min(k, h * w)]]
+
+
+def atss_assign(anchors: np.ndarray, levels, boxes: np.ndarray, topk: int = ATSS_TOPK) -> dict:
+    """ATSS for one image in float64, brute force: the specification of the HIP kernels and the torch form.
+
+    ``boxes`` (n, 4+).  Returns ``arg`` (A,) the box of every anchor or -1, ``best`` (A,) its IoU or -1,
+    ``threshold`` (n,), ``selected`` (n, L, topk) location indices per level in selection order (-1 padded),
+    ``candidates`` (n, N) anchor indices, ``iou`` (n, N) their IoU with the box and ``inside`` (n, N) whether their
+    grid centre lies inside it."""
+    topk = _check_topk(topk)
+    anchors = np.asarray(anchors, dtype=np.float64)
+    A = anchors.shape[0]
+    lv, A0 = _check_levels(levels, A)
+    boxes = np.asarray(boxes, dtype=np.float64)
+    boxes = boxes.reshape(-1, boxes.shape[-1] if boxes.ndim > 1 else 4)
+    n, L = boxes.shape[0], lv.shape[0]
+    N = int(sum(min(topk, h * w) for _, h, w, _ in lv) * A0)
+    out = {"arg": np.full(A, -1, dtype=np.int64), "best": np.full(A, -1.0), "threshold": np.zeros(n),
+           "selected": np.full((n, L, topk), -1, dtype=np.int64), "candidates": np.zeros((n, N), dtype=np.int64),
+           "iou": np.zeros((n, N)), "inside": np.zeros((n, N), dtype=bool)}
+    for g in range(n):
+        x1, y1, x2, y2 = boxes[g, :4]
+        gcx, gcy = (x1 + x2) / 2, (y1 + y2) / 2
+        cand, ccx, ccy = [], [], []
+        for l, (first, h, w, stride) in enumerate(lv):
+            loc = _nearest_locations(h, w, stride, gcx, gcy, topk)
+            out["selected"][g, l, :len(loc)] = loc
+            cand.append((first + loc[:, None] * A0 + np.arange(A0)[None, :]).ravel())
+            ccx.append(np.repeat((loc % w + 0.5) * stride, A0))
+            ccy.append(np.repeat((loc // w + 0.5) * stride, A0))
+        cand, ccx, ccy = np.concatenate(cand), np.concatenate(ccx), np.concatenate(ccy)
+        iou = compute_overlap(anchors[cand], boxes[g:g + 1, :4])[:, 0]
+        thr = iou.mean() + (iou.std(ddof=1) if iou.size > 1 else 0.0)
+        inside = np.minimum(np.minimum(ccx - x1, ccy - y1), np.minimum(x2 - ccx, y2 - ccy)) > ATSS_INSIDE_EPS
+        take = inside & (iou >= thr) & (iou > out["best"][cand])          # strict: the lower box index keeps a tie
+        out["best"][cand[take]] = iou[take]
+        out["arg"][cand[take]] = g
+        out["threshold"][g] = thr
+        out["candidates"][g] = cand
+        out["iou"][g] = iou
+        out["inside"][g] = inside
+    return out
+
+
+def atss_targets_bbox(image_shape, annotations: np.ndarray, num_classes: int, mask_shape=None, topk: int = ATSS_TOPK,
+                      shapes_callback=None, anchors: Optional[np.ndarray] = None):
+    """ATSS targets for one image, the float64 oracle; returns like ``anchor_targets_bbox``:
+    ``(labels (A, C) with -1 rows for ignore, regression (A, 4), state (A,))``.
+
+    Every box takes, on every level, the ``min(topk, h * w)`` locations whose grid centre is nearest to its own
+    (ties to the lower index) and all anchors there as candidates; its threshold is mean + unbiased std of their
+    IoUs; a candidate at or above it whose grid centre lies inside the box is positive, for the box of largest IoU
+    when for several (ties to the lower box).  Everything else is negative with a zero regression target -- there is
+    no ignore band -- except that anchors centred outside the image are ignored, positives included."""
+    if anchors is None:
+        anchors = anchors_for_shape(image_shape, shapes_callback=shapes_callback)
+    anchors = np.asarray(anchors, dtype=np.float64)
+    A = anchors.shape[0]
+    annotations = np.asarray(annotations, dtype=np.float64).reshape(-1, 5)
+    r = atss_assign(anchors, level_table(image_shape, shapes_callback), annotations, topk)
+    pos = r["arg"] >= 0
+    labels = np.zeros((A, num_classes))
+    state = np.zeros((A,))
+    regression = np.zeros((A, 4))
+    if pos.any():
+        matched = annotations[r["arg"][pos]]
+        labels[np.nonzero(pos)[0], matched[:, 4].astype(int)] = 1
+        state[pos] = 1
+        regression[pos] = bbox_transform(anchors[pos], matched[:, :4])
+    mh, mw = (image_shape if mask_shape is None else mask_shape)[:2]
+    cx = (anchors[:, 0] + anchors[:, 2]) / 2
+    cy = (anchors[:, 1] + anchors[:, 3]) / 2
+    outside = (cx >= mw) | (cy >= mh)
+    labels[outside, :] = -1
+    state[outside] = -1
+    return labels, regression, state
+
+
+def atss_targets_torch(anchors: torch.Tensor, levels, gt: torch.Tensor, gt_count: torch.Tensor,
+                       mask_hw: torch.Tensor, topk: int = ATSS_TOPK, centers: Optional[torch.Tensor] = None,
+                       return_aux: bool = False):
+    """Batched fp32 ATSS targets (CPU devices and ``target_backend="torch"``); arguments and results as
+    ``anchor_targets_torch`` plus the level table.  With ``return_aux`` also ``(threshold (B, G), selected
+    (B, G, L, topk) int32 location indices, -1 padded)``; rows at or beyond ``gt_count`` hold inf and -1.
+
+    The distances are computed as the HIP kernel computes them -- every product and sum rounded to fp32 on its own
+    -- so both select the same locations bit for bit; nothing here depends on the data in shape or control flow."""
+    topk = _check_topk(topk)
+    B, G = gt.shape[0], gt.shape[1]
+    A = anchors.shape[0]
+    dev = anchors.device
+    lv, A0 = _check_levels(levels, A)
+    L = lv.shape[0]
+    f32 = torch.float32
+    gt = gt.to(f32)
+    cnt = gt_count.to(dev).to(torch.int64)
+    valid = torch.arange(G, device=dev)[None, :] < cnt[:, None]                    # (B, G)
+    # rows past the count may hold anything: they are replaced before any arithmetic
+    box = torch.where(valid[..., None], gt[..., :4], torch.zeros((), dtype=f32, device=dev))
+    x1, y1, x2, y2 = box.unbind(-1)
+    gcx, gcy = (x1 + x2) * 0.5, (y1 + y2) * 0.5
+    sel = torch.full((B, G, L, topk), -1, dtype=torch.int32, device=dev)
+    cand, ccx, ccy = [], [], []
+    for l, (first, h, w, stride) in enumerate(lv.tolist()):
+        k = min(topk, h * w)
+        dx = ((torch.arange(w, device=dev, dtype=f32) + 0.5) * float(stride))[None, None, None, :] - gcx[..., None, None]
+        dy = ((torch.arange(h, device=dev, dtype=f32) + 0.5) * float(stride))[None, None, :, None] - gcy[..., None, None]
+        d2 = ((dx * dx) + (dy * dy)).reshape(B, G, h * w)
+        loc = torch.sort(d2, dim=-1, stable=True)[1][..., :k]                      # (d2, index) order
+        sel[:, :, l, :k] = loc.to(torch.int32)
+        cand.append((first + loc[..., None] * A0 + torch.arange(A0, device=dev)).reshape(B, G, k * A0))
+        ccx.append((((loc % w).to(f32) + 0.5) * float(stride)).repeat_interleave(A0, dim=-1))
+        ccy.append(((torch.div(loc, w, rounding_mode="floor").to(f32) + 0.5) * float(stride))
+                   .repeat_interleave(A0, dim=-1))
+    cand, ccx, ccy = torch.cat(cand, -1), torch.cat(ccx, -1), torch.cat(ccy, -1)  # (B, G, N)
+    N = cand.shape[-1]
+    ca = anchors[cand]                                                             # (B, G, N, 4)
+    ax1, ay1, ax2, ay2 = ca.unbind(-1)
+    gx1, gy1, gx2, gy2 = x1[..., None], y1[..., None], x2[..., None], y2[..., None]
+    iw = torch.minimum(ax2, gx2) - torch.maximum(ax1, gx1) + 1
+    ih = torch.minimum(ay2, gy2) - torch.maximum(ay1, gy1) + 1
+    inter = iw * ih
+    ua = (ax2 - ax1 + 1) * (ay2 - ay1 + 1) + (gx2 - gx1 + 1) * (gy2 - gy1 + 1) - inter
+    iou = torch.where((iw > 0) & (ih > 0), inter / ua, torch.zeros_like(inter))
+    mean = iou.sum(-1, keepdim=True) / N
+    dev2 = ((iou - mean) * (iou - mean)).sum(-1, keepdim=True)
+    thr = mean + (torch.sqrt(dev2 / (N - 1)) if N > 1 else torch.zeros_like(mean))  # (B, G, 1)
+    inside = torch.minimum(torch.minimum(ccx - gx1, ccy - gy1), torch.minimum(gx2 - ccx, gy2 - ccy)) > ATSS_INSIDE_EPS
+    pos = inside & (iou >= thr) & valid[..., None]
+    # per anchor: the largest IoU among the boxes it is positive for, then the lowest such box
+    key = (torch.arange(B, device=dev)[:, None, None] * A + cand).reshape(-1)
+    score = torch.where(pos, iou, torch.full_like(iou, -1.0)).reshape(-1)
+    best = torch.full((B * A,), -1.0, dtype=f32, device=dev).scatter_reduce(0, key, score, "amax", include_self=True)
+    won = pos.reshape(-1) & (score == best[key])
+    gidx = torch.arange(G, device=dev)[None, :, None].expand(B, G, N).reshape(-1)
+    arg = torch.full((B * A,), G, dtype=torch.int64, device=dev).scatter_reduce(
+        0, key, torch.where(won, gidx, torch.full_like(gidx, G)), "amin", include_self=True).reshape(B, A)
+    is_pos = arg < G
+    if G > 0:
+        matched = torch.gather(gt, 1, arg.clamp(max=G - 1)[..., None].expand(B, A, 5))
+    else:
+        matched = torch.zeros((B, A, 5), dtype=f32, device=dev)
+    a1, b1, a2, b2 = anchors.unbind(-1)
+    aw, ah = (a2 - a1)[None], (b2 - b1)[None]
+    reg = torch.stack([(matched[..., 0] - a1[None]) / aw, (matched[..., 1] - b1[None]) / ah,
+                       (matched[..., 2] - a2[None]) / aw, (matched[..., 3] - b2[None]) / ah], -1)
+    reg = (reg - BOX_MEAN) / BOX_STD
+    reg = torch.where(is_pos[..., None], reg, torch.zeros_like(reg))
+    label = torch.where(is_pos, matched[..., 4].to(torch.int32), torch.zeros((), dtype=torch.int32, device=dev))
+    state = is_pos.to(torch.int8)
+    if centers is None:
+        centers = torch.from_numpy(centers_round_down(anchors.double().cpu().numpy())).to(dev)
+    mh = mask_hw[:, 0].to(dev).to(f32)[:, None]
+    mw = mask_hw[:, 1].to(dev).to(f32)[:, None]
+    outside = (centers[None, :, 0] >= mw) | (centers[None, :, 1] >= mh)
+    state = torch.where(outside, torch.full_like(state, -1), state)
+    if return_aux:
+        thr = torch.where(valid, thr[..., 0], torch.full_like(thr[..., 0], float("inf")))
+        sel = torch.where(valid[..., None, None], sel, torch.full_like(sel, -1))
+        return state, label, reg, thr, sel
     return state, label, reg

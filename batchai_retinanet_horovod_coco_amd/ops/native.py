@@ -50,6 +50,8 @@ _SIGS = {
     "mxr_loss_grid": [],
     "mxr_anchor_targets": [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_float, c_float,
                            c_float, c_vp],
+    "mxr_atss_targets": [c_vp, c_vp, c_int, ctypes.POINTER(c_int), c_int, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp,
+                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_float, c_vp],
     "mxr_chunk_struct_sizes": [c_vp],
     "mxr_adam_step": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_float, c_float,
                       c_float, c_vp],
@@ -433,6 +435,40 @@ def anchor_targets(anchors, gt, gt_count, image_hw, neg=0.4, pos=0.5, std=0.2, c
     _chk(lib().mxr_anchor_targets(_p(anchors.contiguous()), _p(centers.contiguous()), A, _p(gtc), B, G, _p(gt_count.to(torch.int32).contiguous()),
                                   _p(image_hw.to(torch.int32).contiguous()), _p(state), _p(label), _p(reg), _p(npos),
                                   neg, pos, std, _s()), "anchor_targets")
+    return state, label, reg, npos
+
+
+def atss_targets(anchors, levels, gt, gt_count, image_hw, topk=9, std=0.2, centers=None, return_aux=False):
+    """ATSS targets (``ops.anchors.atss_targets_bbox`` is the specification).  ``levels``: the host level table,
+    (L, 4) rows ``(first anchor index, h, w, stride)`` (``AnchorCache.levels``).  Returns like ``anchor_targets``;
+    with ``return_aux`` also pass 1's ``(threshold (B, G) f32, selected (B, G, L, 16) int32 location indices in
+    selection order, -1 padded)``, inf and -1 for rows at or beyond ``gt_count``."""
+    from .anchors import _check_levels, _check_topk, centers_round_down
+    B, G = gt.shape[0], gt.shape[1]
+    A = anchors.shape[0]
+    dev = anchors.device
+    topk = _check_topk(topk)
+    lv, _ = _check_levels(levels, A)
+    L = lv.shape[0]
+    if L > MAXLEV:
+        raise ValueError("atss_targets takes at most {} levels, got {}".format(MAXLEV, L))
+    table = (c_int * (4 * L))(*[int(v) for v in lv.reshape(-1)])
+    state = torch.empty((B, A), dtype=torch.int8, device=dev)
+    label = torch.empty((B, A), dtype=torch.int32, device=dev)
+    reg = torch.empty((B, A, 4), dtype=torch.float32, device=dev)
+    npos = torch.empty(1, dtype=torch.int32, device=dev)
+    thr = torch.empty((B, G), dtype=torch.float32, device=dev)
+    cut = torch.empty((B, G, L), dtype=torch.int64, device=dev)
+    sel = torch.empty((B, G, L, 16), dtype=torch.int32, device=dev) if return_aux else None
+    gtc = gt.float().contiguous()
+    if centers is None:
+        centers = torch.from_numpy(centers_round_down(anchors.double().cpu().numpy())).to(dev)
+    _chk(lib().mxr_atss_targets(_p(anchors.contiguous()), _p(centers.contiguous()), A, table, L, _p(gtc), B, G,
+                                _p(gt_count.to(torch.int32).contiguous()), _p(image_hw.to(torch.int32).contiguous()),
+                                topk, _p(thr), _p(cut), _p(sel), _p(state), _p(label), _p(reg), _p(npos), std, _s()),
+         "atss_targets")
+    if return_aux:
+        return state, label, reg, npos, thr, sel
     return state, label, reg, npos
 
 

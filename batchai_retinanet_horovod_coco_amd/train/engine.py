@@ -54,8 +54,15 @@ class Trainer:
                  clip_mode: str = "local", compression=None, bucket_bytes: Optional[int] = None,
                  device: Optional[torch.device] = None, overlap: bool = True, target_backend: str = "auto",
                  optimizer: str = "adam", momentum: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0,
-                 ema_decay: float = 0.0, regression_loss: str = "smooth_l1", regression_weight: float = 1.0):
+                 ema_decay: float = 0.0, regression_loss: str = "smooth_l1", regression_weight: float = 1.0,
+                 assigner: str = "iou", atss_topk: int = anchor_ops.ATSS_TOPK):
         from ..parallel.collectives import Compression
+        if assigner not in ("iou", "atss"):
+            raise ValueError("assigner must be 'iou' or 'atss', got {!r}".format(assigner))
+        if assigner == "iou" and atss_topk != anchor_ops.ATSS_TOPK:
+            raise ValueError("atss_topk goes with assigner='atss'; the fixed-threshold rule has no top-k")
+        self.assigner = assigner
+        self.atss_topk = anchor_ops._check_topk(atss_topk)
         if regression_loss != "smooth_l1" and regression_loss not in losses.IOU_KINDS:
             raise ValueError("regression_loss must be 'smooth_l1' or one of {}, got {!r}".format(
                 losses.IOU_KINDS, regression_loss))
@@ -82,6 +89,10 @@ class Trainer:
             # what a snapshot records about the loss (io.checkpoint.training_config reads it off the optimizer)
             self.base_optimizer.regression_loss = regression_loss
             self.base_optimizer.regression_weight = self.regression_weight
+        if assigner != "iou":
+            # likewise the target assignment
+            self.base_optimizer.assigner = assigner
+            self.base_optimizer.atss_topk = self.atss_topk
         self.anchors = anchor_ops.AnchorCache()
         self.num_classes = model.num_classes
         self.target_backend = target_backend
@@ -116,6 +127,13 @@ class Trainer:
         from ..ops import native
         use_hip = (self.target_backend == "hip" or
                    (self.target_backend == "auto" and anchors.is_cuda and native.available()))
+        if self.assigner == "atss":
+            levels = self.anchors.levels((H, W), self.device, self.shapes_callback)
+            if use_hip:
+                return native.atss_targets(anchors, levels, gt, gt_count, image_hw, topk=self.atss_topk, centers=centers)
+            state, label, reg = anchor_ops.atss_targets_torch(anchors, levels, gt, gt_count, image_hw,
+                                                              topk=self.atss_topk, centers=centers)
+            return state, label, reg, (state == 1).sum().to(torch.int32).reshape(1)
         if use_hip:
             return native.anchor_targets(anchors, gt, gt_count, image_hw, centers=centers)
         state, label, reg = anchor_ops.anchor_targets_torch(anchors, gt, gt_count, image_hw, centers=centers)
