@@ -8,7 +8,7 @@ Same subcommands, flags, defaults and argument checks as ``/root/reference/train
 ``--no-evaluation``, ``--freeze-backbone``, ``--random-transform``, ``--image-min-side``,
 ``--image-max-side``), plus a ``synthetic`` dataset and MI355X options (``--dtype``, ``--clip-mode``,
 ``--bucket-mb``, ``--allreduce-dtype``, ``--workers``, ``--shard-data``, ``--checkpoint-format``,
-``--lr``, ``--clipnorm``, ``--optimizer``, ``--momentum``, ``--nesterov``, ``--weight-decay``, ``--ema-decay``, ``--weights-ema``, ``--regression-loss``, ``--regression-weight``, ``--warmup-epochs``, ``--seed``, ``--log-every``, ``--no-metric-average``, ``--log-all-ranks``,
+``--lr``, ``--clipnorm``, ``--optimizer``, ``--momentum``, ``--nesterov``, ``--weight-decay``, ``--ema-decay``, ``--weights-ema``, ``--regression-loss``, ``--regression-weight``, ``--classification-loss``, ``--warmup-epochs``, ``--seed``, ``--log-every``, ``--no-metric-average``, ``--log-all-ranks``,
 ``--metrics-jsonl``, ``--stop-on-nan``, ``--graph``, ``--graph-shapes``, ``--eval-batch-size``,
 ``--eval-pad-multiple``, ``--eval-workers``).
 
@@ -57,6 +57,7 @@ def check_args(parsed_args):
     resolve_optimizer(parsed_args)
     resolve_regression_loss(parsed_args)
     resolve_assigner(parsed_args)
+    resolve_classification_loss(parsed_args)
     if getattr(parsed_args, "warmup_epochs", 0) < 0:
         raise SystemExit("--warmup-epochs must be >= 0")
     if not 0.0 <= getattr(parsed_args, "ema_decay", 0.0) < 1.0:
@@ -122,6 +123,28 @@ def resolve_regression_loss(parsed_args):
         raise SystemExit("--regression-weight must be positive")
     if parsed_args.regression_loss == "smooth_l1" and parsed_args.regression_weight != 1.0:
         raise SystemExit("--regression-weight goes with --regression-loss giou, diou or ciou; smooth_l1 has no weight")
+    return parsed_args
+
+
+def resolve_classification_loss(parsed_args):
+    """``--classification-loss`` when given, else what ``--snapshot`` stores, else focal.  The loss has no state, so
+    a flag that differs from the snapshot wins, with a warning.  The IoU-aware losses do not go with ``--dtype fp8``
+    (the classification final's loss is part of the fp8 epilogue)."""
+    if not hasattr(parsed_args, "classification_loss"):
+        return parsed_args
+    stored = None
+    if parsed_args.snapshot and os.path.exists(parsed_args.snapshot):
+        from ..io import checkpoint
+        stored = checkpoint.stored_classification_loss(parsed_args.snapshot)
+    if parsed_args.classification_loss is None:
+        parsed_args.classification_loss = stored if stored in ("focal", "qfl", "vfl") else "focal"
+    elif stored is not None and stored != parsed_args.classification_loss:
+        warnings.warn("--classification-loss {} differs from --snapshot {}, which was trained with {}: training on "
+                      "with {}".format(parsed_args.classification_loss, parsed_args.snapshot, stored,
+                                       parsed_args.classification_loss))
+    if parsed_args.classification_loss != "focal" and getattr(parsed_args, "dtype", None) == "fp8":
+        raise SystemExit("--classification-loss {} cannot be combined with --dtype fp8: the classification final's "
+                         "focal loss is part of the fp8 epilogue".format(parsed_args.classification_loss))
     return parsed_args
 
 
@@ -268,6 +291,13 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--regression-weight", type=float, default=None, metavar="W",
                         help="Weight of the IoU regression loss against the focal loss (default 1, or what --snapshot "
                              "stores; not with smooth_l1).")
+    parser.add_argument("--classification-loss", choices=["focal", "qfl", "vfl"], default=None,
+                        help="Classification loss.  focal (default): the reference's.  qfl (Quality Focal Loss), vfl "
+                             "(Varifocal Loss): the label class of a positive anchor is trained towards the IoU of its "
+                             "predicted box with its target box, every other class towards 0; loss and gradient in one "
+                             "fused kernel, divided by the number of positive anchors.  Not with --dtype fp8.  With "
+                             "--snapshot the loss stored in the file is used unless this flag is given; the flag wins "
+                             "(the loss has no state).")
     parser.add_argument("--assigner", choices=["iou", "atss"], default=None,
                         help="Anchor target assignment.  iou (default): the reference's fixed thresholds (IoU >= 0.5 "
                              "positive, 0.4-0.5 ignored).  atss: adaptive training sample selection -- every box takes "
@@ -547,6 +577,8 @@ def main(args=None):
                       **(dict(regression_loss=args.regression_loss, regression_weight=args.regression_weight)
                          if args.regression_loss != "smooth_l1" else {}),
                       **(dict(assigner="atss", atss_topk=args.atss_topk) if args.assigner == "atss" else {}),
+                      **(dict(classification_loss=args.classification_loss)
+                         if args.classification_loss != "focal" else {}),
                       **(dict(optimizer="sgd", momentum=args.momentum, nesterov=args.nesterov,
                               weight_decay=args.weight_decay) if args.optimizer == "sgd" else {}))
     if args.snapshot is not None:

@@ -124,6 +124,14 @@ def stored_regression_weight(path: str) -> float:
     return float((_stored_training_config(path) or {}).get("regression_weight", 1.0))
 
 
+def stored_classification_loss(path: str) -> Optional[str]:
+    """The classification loss a checkpoint was trained with -- ``focal``, ``qfl`` or ``vfl`` -- (None when it stores
+    no training config)."""
+    cfg = _stored_training_config(path)
+    name = (cfg or {}).get("loss", {}).get("classification")
+    return name.lstrip("_") if name else None
+
+
 def stored_assigner(path: str) -> Optional[str]:
     """The target assignment a checkpoint was trained with -- ``iou`` (the fixed thresholds) or ``atss`` -- (None when
     it stores no training config)."""
@@ -148,8 +156,10 @@ def _class_mismatch(path: str, optimizer) -> bool:
 def training_config(optimizer) -> Dict:
     cfg = optimizer.get_config() if optimizer is not None else {}
     out = {"optimizer_config": {"class_name": optimizer_class(optimizer) or "Adam", "config": cfg},
-           # the Trainer marks its optimizer with an IoU regression loss; without one it is the reference's
-           "loss": {"regression": "_" + getattr(optimizer, "regression_loss", "smooth_l1"), "classification": "_focal"},
+           # the Trainer marks its optimizer with an IoU regression loss or an IoU-aware classification loss; without
+           # one it is the reference's
+           "loss": {"regression": "_" + getattr(optimizer, "regression_loss", "smooth_l1"),
+                    "classification": "_" + getattr(optimizer, "classification_loss", "focal")},
            "metrics": [], "sample_weight_mode": None, "loss_weights": None}
     if getattr(optimizer, "regression_weight", 1.0) != 1.0:
         out["regression_weight"] = float(optimizer.regression_weight)

@@ -14,6 +14,9 @@ Behavioural spec: keras-retinanet ``losses.focal(alpha=0.25, gamma=2.0)`` and
   used on the CPU.
 * ``iou_loss`` (GIoU / DIoU / CIoU of the decoded boxes, ``Trainer(regression_loss=...)``) takes smooth-L1's place
   on request: the torch expression here is the CPU path and the oracle of ``iou_loss_kernel``.
+* ``quality_loss`` (Quality Focal / Varifocal loss, ``Trainer(classification_loss=...)``) takes focal's place on
+  request: the label class of a positive anchor is trained towards ``quality_targets``, the IoU of its predicted box.
+  The torch expression here is the CPU path and, in float64, the oracle of ``csrc/kernels/quality_loss.hip``.
 """
 from __future__ import annotations
 
@@ -152,6 +155,71 @@ def iou_loss(reg: torch.Tensor, reg_t: torch.Tensor, state: torch.Tensor, anchor
     if backend == "hip":
         return native.IoULossFn.apply(reg, reg_t, state, anchors, kind, weight)
     return _iou_loss_torch(reg, reg_t, state, anchors, kind, weight)
+
+
+CLS_KINDS = ("qfl", "vfl")
+VFL_ALPHA = 0.75
+
+
+def quality_targets(anchors: torch.Tensor, reg: torch.Tensor, reg_t: torch.Tensor, state: torch.Tensor) -> torch.Tensor:
+    """Per row the soft target of the IoU-aware classification losses: the IoU of the decoded predicted box with the
+    decoded target box, exactly ``iou_loss_rows``' ``iou``; 0 where the state is not 1.  reg / reg_t (B, A, 4) deltas,
+    anchors (A, 4), state (B, A); returns (B, A) in the dtype of ``reg``, detached (a constant in the backward)."""
+    from .boxes import bbox_transform_inv
+    A = anchors.shape[0]
+    dt = reg.dtype
+    an = anchors.to(dt)[None]
+    with torch.no_grad():
+        gx1, gy1, gx2, gy2 = bbox_transform_inv(an, reg_t.to(dt).reshape(-1, A, 4)).unbind(-1)
+        qx1, qy1, qx2, qy2 = bbox_transform_inv(an, reg.reshape(-1, A, 4)).unbind(-1)
+        px1, px2 = torch.minimum(qx1, qx2), torch.maximum(qx1, qx2)
+        py1, py2 = torch.minimum(qy1, qy2), torch.maximum(qy1, qy2)
+        iw = (torch.minimum(px2, gx2) - torch.maximum(px1, gx1)).clamp_min(0)
+        ih = (torch.minimum(py2, gy2) - torch.maximum(py1, gy1)).clamp_min(0)
+        inter = iw * ih
+        union = (px2 - px1) * (py2 - py1) + (gx2 - gx1) * (gy2 - gy1) - inter + IOU_EPS
+        q = inter / union
+        return torch.where(state.reshape(-1, A) == 1, q, torch.zeros_like(q))
+
+
+def _softplus(x):
+    return x.clamp_min(0) + torch.log1p(torch.exp(-x.abs()))
+
+
+def _quality_torch(logits, reg, reg_t, state, label, anchors, kind):
+    x = logits if logits.dtype == torch.float64 else logits.float()
+    B, A, C = x.shape
+    q = quality_targets(anchors, reg.to(x.dtype), reg_t, state)
+    pos = (state == 1)
+    keep = (state != -1)[..., None].to(x.dtype)
+    t = torch.zeros_like(x)
+    t.scatter_(2, label.clamp(0, C - 1).long()[..., None], q[..., None])
+    sp = _softplus(x)
+    # sigmoid as exp(-softplus(-x)): the backward of torch.sigmoid, p (1 - p), loses 1 - p from x = 17 on in fp32
+    p = torch.exp(-_softplus(-x))
+    if kind == "qfl":
+        elem = (p - t) ** 2 * (sp - t * x)
+    else:
+        elem = torch.where(t > 0, t * (sp - t * x), VFL_ALPHA * p * p * sp)
+    loss = (elem * keep).sum()
+    return loss / torch.clamp(pos.sum().to(x.dtype), min=1.0)
+
+
+def quality_loss(logits: torch.Tensor, reg: torch.Tensor, reg_t: torch.Tensor, state: torch.Tensor,
+                 label: torch.Tensor, anchors: torch.Tensor, kind: str, backend: str = "auto") -> torch.Tensor:
+    """Quality Focal Loss (``kind="qfl"``: Li et al. 2020, beta = 2) or Varifocal Loss (``"vfl"``: Zhang et al. 2021,
+    alpha = 0.75, gamma = 2) on logits (B, A, C): the label class of a positive anchor is trained towards
+    ``quality_targets`` (the IoU of its predicted box, no gradient into ``reg``), every other class towards 0.  Summed
+    over the anchors whose state is not -1 and divided by max(1, #positives), without Keras' probability clip.  The
+    torch expression computes in fp32, or in float64 when the logits are float64 (the kernel's oracle)."""
+    from . import native
+    if kind not in CLS_KINDS:
+        raise ValueError("kind must be one of {}, got {!r}".format(CLS_KINDS, kind))
+    if backend == "auto":
+        backend = "hip" if (logits.is_cuda and native.available()) else "torch"
+    if backend == "hip":
+        return native.QualityLossFn.apply(logits, reg, reg_t, state, label, anchors, kind)
+    return _quality_torch(logits, reg, reg_t, state, label, anchors, kind)
 
 
 def focal_loss(logits: torch.Tensor, state: torch.Tensor, label: torch.Tensor,

@@ -47,6 +47,8 @@ _SIGS = {
     "mxr_smooth_l1_fwd_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_float, c_int, c_int, c_int, c_vp],
     "mxr_iou_loss_fwd_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_int, c_float, c_int, c_int,
                              c_int, c_vp],
+    "mxr_quality_loss_fwd_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_int, c_int,
+                                 c_int, c_int, c_int, c_vp],
     "mxr_loss_grid": [],
     "mxr_anchor_targets": [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_float, c_float,
                            c_float, c_vp],
@@ -375,6 +377,61 @@ def iou_loss_fwd_bwd(reg, reg_t, anchors, state, npos=None, kind="giou", weight=
                                     _p(state.contiguous()), _p(npos), _p(grad), _p(part), _p(out), rows, A,
                                     IOU_KINDS[kind], weight, _dt(reg), int(group) if ld else 0, ld, _s()), "iou_loss")
     return out.reshape(()), grad
+
+
+CLS_KINDS = {"qfl": 0, "vfl": 1}
+
+
+def quality_loss_fwd_bwd(logits, reg, reg_t, anchors, state, label, npos=None, kind="qfl", grad_out=None, group=0):
+    """Quality Focal / Varifocal loss (``quality_loss.hip``): returns (loss 0-d f32, dlogits like logits), dlogits
+    already / max(1, npos).  The label element of a positive row is trained towards the IoU of the row's decoded
+    prediction ``reg`` with its decoded target ``reg_t`` (a constant: nothing flows into ``reg``).  ``anchors``
+    (A, 4) f32 are those of one image; row r uses anchor r % A.  ``grad_out`` / ``group``: as in
+    :func:`focal_fwd_bwd`."""
+    if kind not in CLS_KINDS:
+        raise ValueError("quality_loss_fwd_bwd: kind must be one of {}, got {!r}".format(sorted(CLS_KINDS), kind))
+    logits = logits.contiguous()
+    reg = reg.contiguous()
+    C = logits.shape[-1]
+    rows = logits.numel() // C if C else 0
+    A = anchors.shape[0]
+    if not (anchors.dim() == 2 and anchors.shape[1] == 4 and anchors.dtype == torch.float32 and A > 0 and C > 0
+            and rows % A == 0 and reg.numel() == rows * 4 and reg_t.numel() == rows * 4 and reg.dtype == logits.dtype
+            and state.numel() == rows and state.dtype == torch.int8 and label.numel() == rows
+            and label.dtype == torch.int32):
+        raise ValueError("quality_loss_fwd_bwd: logits (rows, C), reg (rows, 4) of the logits' dtype, reg_t (rows, 4), "
+                         "state (rows,) int8, label (rows,) int32 and anchors (A, 4) f32 with rows a multiple of A "
+                         "expected")
+    npos = _npos(state, npos)
+    ld = 0
+    if grad_out is not None:
+        ld = grad_out.shape[-1]
+        if not (grad_out.is_contiguous() and grad_out.dtype == logits.dtype and group > 0
+                and grad_out.numel() == rows // group * ld):
+            raise ValueError("quality_loss_fwd_bwd: grad_out does not match the padded layout")
+        grad = grad_out
+    else:
+        grad = torch.empty_like(logits)
+    part = torch.empty(LOSS_GRID, dtype=torch.float32, device=logits.device)
+    out = torch.empty(1, dtype=torch.float32, device=logits.device)
+    _chk(lib().mxr_quality_loss_fwd_bwd(_p(logits), _p(reg), _p(reg_t.float().contiguous()), _p(anchors.contiguous()),
+                                        _p(state.contiguous()), _p(label.contiguous()), _p(npos), _p(grad), _p(part),
+                                        _p(out), rows, C, A, CLS_KINDS[kind], _dt(logits), int(group) if ld else 0, ld,
+                                        _s()), "quality_loss")
+    return out.reshape(()), grad
+
+
+class QualityLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, reg, reg_t, state, label, anchors, kind, npos=None):
+        loss, grad = quality_loss_fwd_bwd(logits, reg.detach(), reg_t, anchors, state, label, npos, kind)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g.to(grad.dtype), None, None, None, None, None, None, None
 
 
 class FocalLossFn(torch.autograd.Function):

@@ -55,8 +55,17 @@ class Trainer:
                  device: Optional[torch.device] = None, overlap: bool = True, target_backend: str = "auto",
                  optimizer: str = "adam", momentum: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0,
                  ema_decay: float = 0.0, regression_loss: str = "smooth_l1", regression_weight: float = 1.0,
-                 assigner: str = "iou", atss_topk: int = anchor_ops.ATSS_TOPK):
+                 assigner: str = "iou", atss_topk: int = anchor_ops.ATSS_TOPK, classification_loss: str = "focal"):
         from ..parallel.collectives import Compression
+        if classification_loss != "focal" and classification_loss not in losses.CLS_KINDS:
+            raise ValueError("classification_loss must be 'focal' or one of {}, got {!r}".format(
+                losses.CLS_KINDS, classification_loss))
+        if classification_loss != "focal":
+            from ..ops import fp8 as _fp8
+            if _fp8.enabled():
+                raise ValueError("classification_loss={!r} does not go with fp8: the classification final's focal loss "
+                                 "is part of the fp8 epilogue".format(classification_loss))
+        self.classification_loss = classification_loss
         if assigner not in ("iou", "atss"):
             raise ValueError("assigner must be 'iou' or 'atss', got {!r}".format(assigner))
         if assigner == "iou" and atss_topk != anchor_ops.ATSS_TOPK:
@@ -89,6 +98,8 @@ class Trainer:
             # what a snapshot records about the loss (io.checkpoint.training_config reads it off the optimizer)
             self.base_optimizer.regression_loss = regression_loss
             self.base_optimizer.regression_weight = self.regression_weight
+        if classification_loss != "focal":
+            self.base_optimizer.classification_loss = classification_loss
         if assigner != "iou":
             # likewise the target assignment
             self.base_optimizer.assigner = assigner
@@ -161,8 +172,9 @@ class Trainer:
 
     def _loss_anchors(self, images):
         """The anchors of the batch's padded shape for the IoU regression losses (the cache's persistent tensor: a
-        captured step keeps a valid pointer); None with smooth-L1, which needs none."""
-        if self.regression_loss == "smooth_l1":
+        captured step keeps a valid pointer) and the IoU-aware classification losses; None with smooth-L1 and focal,
+        which need none."""
+        if self.regression_loss == "smooth_l1" and self.classification_loss == "focal":
             return None
         return self.anchors.get((int(images.shape[1]), int(images.shape[2])), self.device, self.shapes_callback)
 
@@ -180,9 +192,42 @@ class Trainer:
         return losses.iou_loss(reg, reg_t, state, anchors, self.regression_loss, self.regression_weight,
                                backend="torch")
 
+    def _check_quality_rows(self, cls, reg, anchors):
+        """An IoU-aware classification loss reads row r of the regression output for row r of the logits."""
+        if not (cls.dim() == 3 and reg.dim() == 3 and reg.shape[:2] == cls.shape[:2] and reg.shape[2] == 4
+                and anchors is not None and anchors.shape[0] == cls.shape[1]):
+            raise ValueError("classification_loss={!r} needs the regression output (B, A, 4) in the row order of the "
+                             "classification output (B, A, C) and the A anchors of the batch's shape; got {} and {}"
+                             .format(self.classification_loss, tuple(reg.shape), tuple(cls.shape)))
+
+    def _classification_fwd_bwd(self, out, reg_t, state, label, npos, anchors, **pad):
+        """The fused classification loss kernel of this trainer: (loss, d loss / d logits)."""
+        from ..ops import native
+        cls = out["classification"]
+        if self.classification_loss == "focal":
+            return native.focal_fwd_bwd(cls, state, label, npos, **pad)
+        from ..ops import fp8 as _fp8
+        if _fp8.enabled():      # switched on after the constructor's check
+            raise RuntimeError("classification_loss={!r} does not go with fp8".format(self.classification_loss))
+        reg = out["regression"].detach()
+        self._check_quality_rows(cls, reg, anchors)
+        return native.quality_loss_fwd_bwd(cls, reg, reg_t, anchors, state, label, npos,
+                                           kind=self.classification_loss, **pad)
+
+    def _classification_torch(self, out, reg_t, state, label, anchors):
+        cls = out["classification"]
+        if self.classification_loss == "focal":
+            return losses.focal_loss(cls, state, label, backend="torch")
+        self._check_quality_rows(cls, out["regression"], anchors)
+        return losses.quality_loss(cls, out["regression"], reg_t, state, label, anchors, self.classification_loss,
+                                   backend="torch")
+
     def _focal_request(self, state, label, npos):
         """This step's targets for the classification final's fused focal loss (bf16 HIP heads with the padded
-        focal gradient), handed to the model for its forward; None where the fusion does not apply."""
+        focal gradient), handed to the model for its forward; None where the fusion does not apply (an IoU-aware
+        classification loss needs the regression output: the final writes its logits and quality_loss.hip reads them)."""
+        if self.classification_loss != "focal":
+            return None
         if not (self._fused_losses() and _PAD_FOCAL and self.compute_dtype == torch.bfloat16
                 and hasattr(self.model, "cls_pad_sink")):
             return None
@@ -228,15 +273,16 @@ class Trainer:
                 # data-gradient rows; autograd carries a zero-stride placeholder
                 key = (cls.shape[0], cls.shape[1] // A, cp, cls.device)
                 buf = self._cls_pad_buf.get(key, lambda: torch.zeros(key[:3], dtype=cls.dtype, device=cls.device))
-                cls_loss, dpad = native.focal_fwd_bwd(cls, state, label, npos, grad_out=buf, group=A)
+                cls_loss, dpad = self._classification_fwd_bwd(out, reg_t, state, label, npos, anchors, grad_out=buf,
+                                                              group=A)
                 sink["dy"] = dpad
                 dcls = torch.zeros((), dtype=cls.dtype, device=cls.device).expand(cls.shape)
             else:
-                cls_loss, dcls = native.focal_fwd_bwd(cls, state, label, npos)
+                cls_loss, dcls = self._classification_fwd_bwd(out, reg_t, state, label, npos, anchors)
             torch.autograd.backward([reg, cls], [dreg, dcls])
         else:
             reg_loss = self._regression_torch(out["regression"], reg_t, state, anchors)
-            cls_loss = losses.focal_loss(out["classification"], state, label, backend="torch")
+            cls_loss = self._classification_torch(out, reg_t, state, label, anchors)
             (reg_loss + cls_loss).backward()
         return reg_loss.detach(), cls_loss.detach()
 
@@ -245,8 +291,9 @@ class Trainer:
         with torch.no_grad():
             state, label, reg_t, npos = self.compute_targets(images, gt, gt_count, image_hw)
             out = self.model(images.to(self.compute_dtype))
-            reg_loss = self._regression_torch(out["regression"], reg_t, state, self._loss_anchors(images))
-            cls_loss = losses.focal_loss(out["classification"], state, label, backend="torch")
+            anchors = self._loss_anchors(images)
+            reg_loss = self._regression_torch(out["regression"], reg_t, state, anchors)
+            cls_loss = self._classification_torch(out, reg_t, state, label, anchors)
         return reg_loss, cls_loss
 
     def train_on_batch(self, images: torch.Tensor, gt: torch.Tensor, gt_count: torch.Tensor,

@@ -116,6 +116,50 @@ __device__ __forceinline__ float focal8_g2(const float (&x)[8], int lb, float al
   return accv;
 }
 
+// The IoU-aware classification losses (--classification-loss qfl / vfl, quality_loss.hip): Quality Focal Loss
+// (Li et al. 2020, beta = 2) and Varifocal Loss (Zhang et al. 2021, alpha = 0.75, gamma = 2) on the logit, without
+// Keras' probability clip.  An element with target 0 (every class of a negative row, every class but the label of
+// a positive one) costs c p^2 softplus(x) in both, c = 1 (QFL) or alpha (VFL): in bf16 that is focal_neg_g2_inr
+// as it stands (gradient c p^2 (2 (1 - p) softplus(x) + p)); quality_neg_f32 is its fp32 form, with the library
+// exp / log1p and a true division for the reason focal_elem_f32 (losses.hip) gives.
+enum { kQFL = 0, kVFL = 1 };
+constexpr float kVflAlpha = 0.75f;
+
+__device__ __forceinline__ void quality_neg_f32(float x, float c_loss, float c_grad, float& loss, float& grad) {
+  const float e = expf(-fabsf(x));
+  const float r = 1.0f / (1.0f + e);
+  const float p = x >= 0.f ? r : e * r;        // sigmoid(x)
+  const float q = x >= 0.f ? e * r : r;        // 1 - sigmoid(x)
+  const float sp = fmaxf(x, 0.f) + log1pf(e);
+  const float p2 = p * p;
+  loss = c_loss * p2 * sp;
+  grad = c_grad * p2 * fmaf(q, sp + sp, p);
+}
+
+// The label element of a positive row, soft target t (the IoU of the row's predicted box with its target box, a
+// constant in the backward).  QFL: (p - t)^2 BCE(t, x); VFL: t BCE(t, x) for t > 0 and the target-0 form for a t
+// of exactly 0, with BCE(t, x) = softplus(x) - t x.  One element in ~80,000, but in a branch that holds up its whole
+// wave: one exp, one log1p and one division serve every case; they are the library's for both input types (p - t
+// cancels, so p wants its last bits).
+__device__ __forceinline__ void quality_pos(float x, float t, int kind, float& loss, float& grad) {
+  const float e = expf(-fabsf(x));
+  const float r = 1.0f / (1.0f + e);
+  const float p = x >= 0.f ? r : e * r;
+  const float q = x >= 0.f ? e * r : r;
+  const float sp = fmaxf(x, 0.f) + log1pf(e);
+  const float bce = sp - t * x;
+  const float d = p - t;
+  if (kind == kVFL) {
+    const bool soft = t > 0.f;
+    const float p2 = kVflAlpha * p * p;
+    loss = soft ? t * bce : p2 * sp;
+    grad = soft ? t * d : p2 * fmaf(q, sp + sp, p);
+  } else {
+    loss = d * d * bce;
+    grad = 2.0f * d * p * q * bce + d * d * d;
+  }
+}
+
 // the classification final's fused focal epilogue (conv_hx32 / conv_hx32_f8 FOC forms): per anchor row
 // (pixel * A + anchor) its state (-1 ignore / 0 negative / 1 positive) and label, the #positives, the padded
 // gradient rows dpad[pixel][ld] (anchor a's C logits at a * C), one loss partial per block
