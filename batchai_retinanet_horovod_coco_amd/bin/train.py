@@ -8,7 +8,7 @@ Same subcommands, flags, defaults and argument checks as ``/root/reference/train
 ``--no-evaluation``, ``--freeze-backbone``, ``--random-transform``, ``--image-min-side``,
 ``--image-max-side``), plus a ``synthetic`` dataset and MI355X options (``--dtype``, ``--clip-mode``,
 ``--bucket-mb``, ``--allreduce-dtype``, ``--workers``, ``--shard-data``, ``--checkpoint-format``,
-``--lr``, ``--clipnorm``, ``--optimizer``, ``--momentum``, ``--nesterov``, ``--weight-decay``, ``--ema-decay``, ``--weights-ema``, ``--regression-loss``, ``--regression-weight``, ``--classification-loss``, ``--warmup-epochs``, ``--seed``, ``--log-every``, ``--no-metric-average``, ``--log-all-ranks``,
+``--lr``, ``--clipnorm``, ``--optimizer``, ``--momentum``, ``--nesterov``, ``--weight-decay``, ``--ema-decay``, ``--weights-ema``, ``--regression-loss``, ``--regression-weight``, ``--classification-loss``, ``--head-norm``, ``--head-norm-groups``, ``--warmup-epochs``, ``--seed``, ``--log-every``, ``--no-metric-average``, ``--log-all-ranks``,
 ``--metrics-jsonl``, ``--stop-on-nan``, ``--graph``, ``--graph-shapes``, ``--eval-batch-size``,
 ``--eval-pad-multiple``, ``--eval-workers``).
 
@@ -58,6 +58,7 @@ def check_args(parsed_args):
     resolve_regression_loss(parsed_args)
     resolve_assigner(parsed_args)
     resolve_classification_loss(parsed_args)
+    resolve_head_norm(parsed_args)
     if getattr(parsed_args, "warmup_epochs", 0) < 0:
         raise SystemExit("--warmup-epochs must be >= 0")
     if not 0.0 <= getattr(parsed_args, "ema_decay", 0.0) < 1.0:
@@ -146,6 +147,49 @@ def resolve_classification_loss(parsed_args):
         raise SystemExit("--classification-loss {} cannot be combined with --dtype fp8: the classification final's "
                          "focal loss is part of the fp8 epilogue".format(parsed_args.classification_loss))
     return parsed_args
+
+
+def resolve_head_norm(parsed_args):
+    """``--head-norm`` / ``--head-norm-groups`` when given, else what the model in ``--snapshot`` stores, else no norm
+    (``head_norm`` None) and 32 groups.  A flag that differs from the snapshot wins, with a warning: the weights both
+    models have are loaded.  ``head_norm_override`` tells whether the snapshot's model is rebuilt with the flags."""
+    if not hasattr(parsed_args, "head_norm"):
+        return parsed_args
+    given, given_g = parsed_args.head_norm, parsed_args.head_norm_groups
+    stored, stored_g, have = None, 32, False
+    if parsed_args.snapshot and os.path.exists(parsed_args.snapshot):
+        from ..io import checkpoint
+        stored, stored_g = checkpoint.stored_head_norm(parsed_args.snapshot)
+        have = True
+    if given is None:
+        norm = stored
+    else:
+        norm = None if given == "none" else given
+        if have and norm != stored:
+            warnings.warn("--head-norm {} differs from --snapshot {}, whose model was built with {}: training on with "
+                          "{}".format(given, parsed_args.snapshot, stored or "none", given))
+    if given_g is not None and norm != "gn":
+        raise SystemExit("--head-norm-groups goes with --head-norm gn; towers without the norm have no groups")
+    groups = given_g if given_g is not None else (stored_g if stored == "gn" else 32)
+    if norm == "gn":
+        if groups < 1 or 256 % groups:
+            raise SystemExit("--head-norm-groups must divide the 256 tower channels, got {}".format(groups))
+        if have and stored == "gn" and groups != stored_g:
+            warnings.warn("--head-norm-groups {} differs from --snapshot {}, whose model was built with {}: training "
+                          "on with {}".format(groups, parsed_args.snapshot, stored_g, groups))
+        if getattr(parsed_args, "dtype", None) == "fp8":
+            raise SystemExit("--head-norm gn cannot be combined with --dtype fp8: the fp8 tower layers hand fp8 "
+                             "copies of their ReLU outputs to each other")
+    parsed_args.head_norm_override = have and (norm != stored or (norm == "gn" and groups != stored_g))
+    parsed_args.head_norm, parsed_args.head_norm_groups = norm, groups
+    return parsed_args
+
+
+def head_norm_kwargs(parsed_args):
+    """The model keywords of the resolved ``--head-norm`` (none for the default towers)."""
+    if getattr(parsed_args, "head_norm", None) != "gn":
+        return {}
+    return dict(head_norm="gn", head_norm_groups=parsed_args.head_norm_groups)
 
 
 def resolve_assigner(parsed_args):
@@ -298,6 +342,15 @@ def build_parser() -> argparse.ArgumentParser:
                              "fused kernel, divided by the number of positive anchors.  Not with --dtype fp8.  With "
                              "--snapshot the loss stored in the file is used unless this flag is given; the flag wins "
                              "(the loss has no state).")
+    parser.add_argument("--head-norm", choices=["none", "gn"], default=None,
+                        help="Normalisation of the head towers.  none (default): the reference's conv + ReLU.  gn: "
+                             "every tower layer of both submodels is conv -> GroupNorm -> ReLU (the heads of ATSS, GFL "
+                             "and VarifocalNet), statistics per image, pyramid level and group, in fused kernels on "
+                             "the packed pyramid.  Not with --dtype fp8.  With --snapshot the stored model's setting "
+                             "is used unless this flag is given; the flag wins, with a warning.")
+    parser.add_argument("--head-norm-groups", type=int, default=None, metavar="G",
+                        help="With --head-norm gn: groups of the 256 tower channels (default 32, or what --snapshot "
+                             "stores; must divide 256).")
     parser.add_argument("--assigner", choices=["iou", "atss"], default=None,
                         help="Anchor target assignment.  iou (default): the reference's fixed thresholds (IoU >= 0.5 "
                              "positive, 0.4-0.5 ignored).  atss: adaptive training sample selection -- every box takes "
@@ -541,14 +594,17 @@ def main(args=None):
     initial_epoch = 0
     if args.snapshot is not None:
         print("Loading model, this may take a second...")
-        model = models.load_model(args.snapshot, backbone_name=args.backbone)
+        model = models.load_model(args.snapshot, backbone_name=args.backbone,
+                                  **(dict(head_norm=args.head_norm, head_norm_groups=args.head_norm_groups)
+                                     if args.head_norm_override else {}))
     else:
         weights = args.weights
         if weights is None and args.imagenet_weights:
             weights = backbone.download_imagenet()
         print("Creating model, this may take a second...")
         model = backbone.retinanet(train_generator.num_classes(),
-                                   modifier=models.freeze if args.freeze_backbone else None)
+                                   modifier=models.freeze if args.freeze_backbone else None,
+                                   **head_norm_kwargs(args))
         if weights is not None:
             checkpoint.load_weights(model, weights, by_name=True, skip_mismatch=True,
                                     **(dict(group="ema_weights") if args.weights_ema else {}))

@@ -68,14 +68,45 @@ def keras_layers(model) -> "OrderedDict[str, List[Tuple[str, torch.Tensor, str]]
         for c in sub.convs():
             ws.extend(conv(c))
         layers[sub.keras_name] = ws
+        # head_norm='gn': each GroupNorm is a layer of its own after its submodel, so files without them still load
+        # by name
+        for n in (getattr(sub, "norms", None) or []):
+            layers[n.keras_name] = [(n.keras_name + "/" + w, t, "plain") for w, t in n.keras_weights()]
     return layers
 
 
+_GN_LAYER = re.compile(r"^pyramid_(regression|classification)_\d+_gn$")
+_GN_TENSOR = re.compile(r"_submodel\.norms\.\d+\.(gamma|beta)$")
+
+
+def _check_head_norm(path: str, model, file_has_gn: bool, strict: bool = True) -> None:
+    """The two cross-loading cases of ``head_norm``: a file without the GroupNorm layers leaves a GN model's gamma /
+    beta at their initial values (one warning); a file with them does not load into a model without the norm."""
+    model_has_gn = getattr(model, "head_norm", None) == "gn"
+    if model_has_gn and not file_has_gn:
+        warnings.warn("{} holds no GroupNorm layers: the head towers' gamma / beta stay at their initial values (1 / 0)"
+                      .format(path))
+    elif file_has_gn and not model_has_gn and strict:
+        raise ValueError("{} holds the GroupNorm layers of head towers trained with --head-norm gn, the model has "
+                         "none: build it with --head-norm gn (head_norm='gn')".format(path))
+
+
 def model_config(model) -> Dict:
-    return {"class_name": "RetinaNet", "framework": FRAMEWORK,
-            "config": {"name": "retinanet", "backbone": model.backbone_name, "num_classes": model.num_classes,
-                       "num_anchors": model.num_anchors,
-                       "layers": list(keras_layers(model).keys())}}
+    cfg = {"class_name": "RetinaNet", "framework": FRAMEWORK,
+           "config": {"name": "retinanet", "backbone": model.backbone_name, "num_classes": model.num_classes,
+                      "num_anchors": model.num_anchors,
+                      "layers": list(keras_layers(model).keys())}}
+    if getattr(model, "head_norm", None) is not None:
+        # only with the norm on: a default model's config stays what it was
+        cfg["config"]["head_norm"] = model.head_norm
+        cfg["config"]["head_norm_groups"] = int(model.head_norm_groups)
+    return cfg
+
+
+def stored_head_norm(path: str) -> Tuple[Optional[str], int]:
+    """(head_norm, head_norm_groups) of the model a checkpoint holds: (None, 32) for one without the norm."""
+    cfg = read_model_config(path).get("config", {})
+    return cfg.get("head_norm"), int(cfg.get("head_norm_groups", 32))
 
 
 def optimizer_class(optimizer) -> Optional[str]:
@@ -251,6 +282,8 @@ def _restore_ema_h5(f, path: str, model, optimizer) -> None:
     flat = optimizer.flat
     with torch.no_grad():
         for lname, ws in keras_layers(model).items():
+            if lname not in g and _GN_LAYER.match(lname):
+                continue            # GroupNorm layers the file does not hold: their average stays the weights
             for wname, t, kind in ws:
                 seg = flat.by_param.get(id(t))
                 if seg is None:
@@ -339,17 +372,19 @@ def has_ema_weights(path: str) -> bool:
 
 
 def load_weights(model, path: str, by_name: bool = True, skip_mismatch: bool = False,
-                 group: str = "model_weights") -> List[str]:
+                 group: str = "model_weights", strict_head_norm: bool = True) -> List[str]:
     """Keras ``load_weights`` (HDF5 or safetensors).  Returns the list of skipped weights.  ``group="ema_weights"``
     loads the averaged set a run with a weight EMA stored; a ValueError when the file has none."""
     if group not in ("model_weights", EMA_GROUP):
         raise ValueError("group must be 'model_weights' or '{}', got {!r}".format(EMA_GROUP, group))
     if path.endswith(".safetensors"):
         return load_safetensors(model, path, optimizer=None, skip_mismatch=skip_mismatch,
-                                prefix=EMA_PREFIX if group == EMA_GROUP else "")[1]
+                                prefix=EMA_PREFIX if group == EMA_GROUP else "", strict_head_norm=strict_head_norm)[1]
     f = hdf5.File(path, "r")
     file_layers = _layer_weights_from_file(f, group)
     layers = keras_layers(model)
+    if by_name:
+        _check_head_norm(path, model, any(_GN_LAYER.match(l) for l in file_layers), strict_head_norm)
     skipped = []
     if not by_name:
         wl = [l for l in layers if layers[l]]
@@ -397,6 +432,19 @@ def load_optimizer_h5(model, optimizer, path: str) -> bool:
     slots = _slots(optimizer)
     if len(names) < 1 + len(slots) * n or not names[0].startswith(optimizer_class(optimizer) + "/"):
         return False
+    # slots are matched by position: a file written for another list of trainable parameters (a model with or without
+    # the head towers' GroupNorm layers) holds none for this model -- judged before anything is touched
+    stored = 3 if optimizer_class(optimizer) == "Adam" else 1          # Adam: m, v and the vhat placeholders
+    fits = len(names) == 1 + stored * n
+    for k in range(len(slots) if fits else 0):
+        for i, (p, kind) in enumerate(params):
+            shape = tuple(ow[names[1 + k * n + i]].shape)
+            want = tuple(p.shape[j] for j in _TO_KERAS[kind]) if kind in _TO_KERAS else tuple(p.shape)
+            fits = fits and shape == want
+    if not fits:
+        warnings.warn("{} holds optimizer state for another list of trainable parameters than the model's: weights "
+                      "loaded, optimizer state left fresh".format(path))
+        return False
     optimizer.iterations = int(np.asarray(ow[names[0]]).reshape(-1)[0])
     flat = optimizer.flat
     with torch.no_grad():
@@ -441,12 +489,18 @@ def checkpoint_epoch(path: str) -> Optional[int]:
 
 
 def load_model(filepath: str, backbone_name: str = "resnet50", **kwargs):
-    """``models.load_model``: rebuild the architecture from the stored config, load weights."""
+    """``models.load_model``: rebuild the architecture from the stored config, load weights.  ``head_norm`` /
+    ``head_norm_groups`` given here win over the stored ones (the weights they have in common are loaded)."""
     from .. import models
     cfg = read_model_config(filepath).get("config", {})
     name = cfg.get("backbone", backbone_name)
-    model = models.backbone(name).retinanet(int(cfg.get("num_classes", kwargs.get("num_classes", 80))))
-    load_weights(model, filepath, by_name=True, skip_mismatch=False)
+    norm = {}
+    head_norm = kwargs["head_norm"] if "head_norm" in kwargs else cfg.get("head_norm")
+    if head_norm not in (None, "none"):
+        norm = dict(head_norm=head_norm,
+                    head_norm_groups=int(kwargs.get("head_norm_groups") or cfg.get("head_norm_groups", 32)))
+    model = models.backbone(name).retinanet(int(cfg.get("num_classes", kwargs.get("num_classes", 80))), **norm)
+    load_weights(model, filepath, by_name=True, skip_mismatch=False, strict_head_norm="head_norm" not in kwargs)
     return model
 
 
@@ -482,7 +536,8 @@ def save_safetensors(path: str, model, optimizer=None, epoch: Optional[int] = No
     return path
 
 
-def load_safetensors(model, path: str, optimizer=None, skip_mismatch: bool = False, prefix: str = ""):
+def load_safetensors(model, path: str, optimizer=None, skip_mismatch: bool = False, prefix: str = "",
+                     strict_head_norm: Optional[bool] = True):
     """Returns (metadata, skipped tensors); ``metadata["optimizer_restored"]`` tells whether the optimizer state was
     restored (only from a file written with the live optimizer's class).  ``prefix="ema/"`` loads the averaged set."""
     from safetensors.torch import load_file
@@ -496,8 +551,13 @@ def load_safetensors(model, path: str, optimizer=None, skip_mismatch: bool = Fal
         sd = {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
     own = model.state_dict()
     skipped = []
+    file_has_gn = any(_GN_TENSOR.search(k) for k in sd)
+    if strict_head_norm is not None:
+        _check_head_norm(path, model, file_has_gn, strict_head_norm)
     with torch.no_grad():
         for k, v in own.items():
+            if not file_has_gn and _GN_TENSOR.search(k):
+                continue            # stays at its initial value (_check_head_norm)
             if k not in sd or tuple(sd[k].shape) != tuple(v.shape):
                 if skip_mismatch:
                     skipped.append(k)
@@ -540,7 +600,8 @@ def load_optimizer(model, optimizer, path: str) -> bool:
     """Optimizer state from a checkpoint of either format; False when the file holds none for this optimizer class
     (a safetensors file's weights are read again on the way)."""
     if path.endswith(".safetensors"):
-        return bool(load_safetensors(model, path, optimizer)[0]["optimizer_restored"])
+        # (the second read of a file whose weights load_weights has judged: no second head_norm warning)
+        return bool(load_safetensors(model, path, optimizer, strict_head_norm=None)[0]["optimizer_restored"])
     return load_optimizer_h5(model, optimizer, path)
 
 

@@ -70,6 +70,27 @@ class FrozenBatchNormalization(nn.Module):
                 ("moving_mean:0", self.moving_mean), ("moving_variance:0", self.moving_variance)]
 
 
+class GroupNorm(nn.Module):
+    """Trainable GroupNorm affine of a head-tower layer (``--head-norm gn``): gamma 1, beta 0, eps 1e-5.  The
+    statistics are per (image, pyramid level, group); gamma and beta are shared by the levels (``ops.norm``)."""
+
+    def __init__(self, name: str, channels: int, groups: int = 32, eps: float = 1e-5):
+        super().__init__()
+        if groups < 1 or channels % groups:
+            raise ValueError("GroupNorm {}: {} groups do not divide {} channels".format(name, groups, channels))
+        self.keras_name = name
+        self.groups = groups
+        self.eps = eps
+        self.gamma = nn.Parameter(torch.ones(channels))
+        self.beta = nn.Parameter(torch.zeros(channels))
+
+    def keras_weights(self):
+        return [("gamma:0", self.gamma), ("beta:0", self.beta)]
+
+    def extra_repr(self) -> str:
+        return "{}: {} channels, {} groups".format(self.keras_name, self.gamma.numel(), self.groups)
+
+
 class Conv2D(nn.Module):
     """Keras Conv2D with NHWC activations and OHWI weights.
 

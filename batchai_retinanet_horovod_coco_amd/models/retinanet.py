@@ -23,7 +23,8 @@ import torch.nn as nn
 from ..ops import anchors as anchor_ops
 from ..ops import boxes as box_ops
 from ..ops import conv as conv_ops
-from .layers import Conv2D, prior_probability_bias
+from ..ops import norm as norm_ops
+from .layers import Conv2D, GroupNorm, prior_probability_bias
 from .resnet import ResNet
 
 
@@ -59,16 +60,38 @@ class FPN(nn.Module):
         return [self.C5_reduced, self.P5, self.C4_reduced, self.P4, self.C3_reduced, self.P3, self.P6, self.P7]
 
 
-class Submodel(nn.Module):
-    """Shared head tower: 4 x (3x3 conv 256 + ReLU) + final 3x3 conv."""
+HEAD_NORMS = (None, "gn")
 
-    def __init__(self, name: str, prefix: str, cin: int, width: int, out_channels: int, final_bias: float):
+
+def check_head_norm(head_norm, head_norm_groups: int, width: int = 256):
+    """``head_norm`` as the model keeps it: None (also for the string 'none') or 'gn' with a group count that
+    divides the tower width."""
+    if head_norm == "none":
+        head_norm = None
+    if head_norm not in HEAD_NORMS:
+        raise ValueError("head_norm must be None or 'gn', got {!r}".format(head_norm))
+    if head_norm == "gn" and (int(head_norm_groups) < 1 or width % int(head_norm_groups)):
+        raise ValueError("head_norm_groups must divide the tower width {}, got {}".format(width, head_norm_groups))
+    return head_norm
+
+
+class Submodel(nn.Module):
+    """Shared head tower: 4 x (3x3 conv 256 + ReLU) + final 3x3 conv; with ``head_norm='gn'`` every tower layer is
+    conv (+ bias) -> GroupNorm(groups) -> ReLU."""
+
+    def __init__(self, name: str, prefix: str, cin: int, width: int, out_channels: int, final_bias: float,
+                 head_norm: Optional[str] = None, head_norm_groups: int = 32):
         super().__init__()
         self.keras_name = name
+        self.head_norm = check_head_norm(head_norm, head_norm_groups, width)
         self.tower = nn.ModuleList(
             [Conv2D(f"{prefix}_{i}", cin if i == 0 else width, width, 3, 1, "same", True, True, "normal001")
              for i in range(4)])
         self.final = Conv2D(prefix, width, out_channels, 3, 1, "same", True, False, "normal001", bias_value=final_bias)
+        # registered only with the norm on: a default model has no new parameter
+        self.norms = None
+        if self.head_norm == "gn":
+            self.norms = nn.ModuleList([GroupNorm(f"{prefix}_{i}_gn", width, int(head_norm_groups)) for i in range(4)])
         if os.environ.get("MXR_HEAD_MAIN_WGRAD", "0") == "1":
             # the head weight gradients on the compute stream, serial with the data gradients (an A/B of the
             # side-stream overlap for the biggest weight gradients: profiles/r6_head_main_wgrad_ab.txt)
@@ -77,9 +100,14 @@ class Submodel(nn.Module):
 
     def forward(self, feats: List[torch.Tensor]) -> List[torch.Tensor]:
         x = feats
-        for c in self.tower:
+        for i, c in enumerate(self.tower):
             w, b = c.effective(x[0].dtype)
-            x = conv_ops.pyramid_conv(x, w, b, relu=True)
+            if self.norms is None:
+                x = conv_ops.pyramid_conv(x, w, b, relu=True)
+            else:
+                n = self.norms[i]
+                x = [norm_ops.group_norm_relu_nhwc(t, n.gamma, n.beta, n.groups, n.eps)
+                     for t in conv_ops.pyramid_conv(x, w, b, relu=False)]
         w, b = self.final.effective(x[0].dtype)
         return conv_ops.pyramid_conv(x, w, b, relu=False)
 
@@ -90,6 +118,18 @@ class Submodel(nn.Module):
         zero-padded rows (see :attr:`RetinaNet.cls_pad_sink`)."""
         from ..ops import native_conv
         from ..ops import fp8
+        if self.norms is not None:
+            # conv -> fused GroupNorm + ReLU (group_norm.hip): the conv leaves its plain output, the norm's backward
+            # applies the ReLU mask it recomputes, so no layer masks its input gradient
+            if fp8.enabled():
+                raise RuntimeError("head_norm='gn' does not go with fp8: the tower layers hand fp8 copies of their "
+                                   "ReLU outputs to each other")
+            for i, (c, n) in enumerate(zip(self.tower, self.norms)):
+                x = native_conv.pyramid_conv_layer(x, shapes, c, False, mask_input_grad=False, grad_premasked=False,
+                                                   join=join if i == 0 else None, out_f8=False)
+                x = norm_ops.group_norm_relu(x, shapes, n.gamma, n.beta, n.groups, n.eps)
+            return native_conv.pyramid_conv_layer(x, shapes, self.final, False, mask_input_grad=False,
+                                                  pad_sink=pad_sink)
         # each tower output feeds only the next layer: its relu backward is fused into that layer's
         # data-gradient epilogue (mask_input_grad) and skipped in its own backward (grad_premasked); out_f8 when
         # that next layer runs fp8 (the regression final's 36 outputs do not)
@@ -109,8 +149,11 @@ class RetinaNet(nn.Module):
     """Training model.  ``forward(images NHWC) -> {'regression', 'classification'}``."""
 
     def __init__(self, num_classes: int, backbone: str = "resnet50", num_anchors: int = 9,
-                 feature_size: int = 256, prior_probability: float = 0.01):
+                 feature_size: int = 256, prior_probability: float = 0.01, head_norm: Optional[str] = None,
+                 head_norm_groups: int = 32):
         super().__init__()
+        self.head_norm = check_head_norm(head_norm, head_norm_groups)
+        self.head_norm_groups = int(head_norm_groups)
         self.num_classes = num_classes
         self.num_anchors = num_anchors
         self.backbone_name = backbone
@@ -122,10 +165,11 @@ class RetinaNet(nn.Module):
         c3, c4, c5 = self.backbone.out_channels[1:]
         self.fpn = FPN(c3, c4, c5, feature_size)
         self.regression_submodel = Submodel("regression_submodel", "pyramid_regression", feature_size, 256,
-                                            num_anchors * 4, 0.0)
+                                            num_anchors * 4, 0.0, self.head_norm, self.head_norm_groups)
         self.classification_submodel = Submodel("classification_submodel", "pyramid_classification", feature_size,
                                                 256, num_anchors * num_classes,
-                                                prior_probability_bias(prior_probability))
+                                                prior_probability_bias(prior_probability), self.head_norm,
+                                                self.head_norm_groups)
 
     def features(self, images: torch.Tensor) -> List[torch.Tensor]:
         joins = self._grad_joins(images)
@@ -199,6 +243,10 @@ class RetinaNet(nn.Module):
 
     def backbone_parameters(self):
         return list(self.backbone.parameters())
+
+    def norms(self) -> List[GroupNorm]:
+        """The head towers' GroupNorm layers (none without ``head_norm``)."""
+        return [n for sub in (self.regression_submodel, self.classification_submodel) for n in (sub.norms or [])]
 
     def freeze_backbone(self) -> None:
         """``utils.model.freeze`` on the backbone (``--freeze-backbone``, train.py:82,375)."""

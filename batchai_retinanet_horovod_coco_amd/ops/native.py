@@ -50,6 +50,9 @@ _SIGS = {
     "mxr_quality_loss_fwd_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_int, c_int,
                                  c_int, c_int, c_int, c_vp],
     "mxr_loss_grid": [],
+    "mxr_gn_chunk_rows": [],
+    "mxr_gn_relu_fwd": [c_vp] * 7 + [c_ll, c_int, c_ll, c_int, c_int, c_float, c_int, ctypes.POINTER(c_int), c_int, c_vp],
+    "mxr_gn_relu_bwd": [c_vp] * 10 + [c_ll, c_int, c_ll, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, c_vp],
     "mxr_anchor_targets": [c_vp, c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_float, c_float,
                            c_float, c_vp],
     "mxr_atss_targets": [c_vp, c_vp, c_int, ctypes.POINTER(c_int), c_int, c_vp, c_int, c_int, c_vp, c_vp, c_int, c_vp,
@@ -471,6 +474,113 @@ class IoULossFn(torch.autograd.Function):
     def backward(ctx, g):
         (grad,) = ctx.saved_tensors
         return grad * g.to(grad.dtype), None, None, None, None, None, None
+
+
+# =========================================================================================
+# GroupNorm + ReLU on the packed pyramid (group_norm.hip)
+# =========================================================================================
+class NotServed(Exception):
+    """An entry point returned -1: the caller falls back to the torch expression."""
+
+
+def _gn_levels(shapes):
+    """(host table of (row offset, pixels) pairs, pixel counts) of packed levels."""
+    npix = [int(h) * int(w) for h, w in shapes]
+    flat, off = [], 0
+    for n in npix:
+        flat += [off, n]
+        off += n
+    return (c_int * max(1, len(flat)))(*flat), npix
+
+
+def _gn_blocks(B: int, npix) -> int:
+    rows = lib().mxr_gn_chunk_rows()
+    return B * sum((n + rows - 1) // rows for n in npix)
+
+
+def _gn_dt(t: torch.Tensor) -> int:
+    return {torch.float32: 0, torch.bfloat16: 1}.get(t.dtype, 2)
+
+
+def gn_served(x: torch.Tensor, groups: int, nlev: int) -> bool:
+    """What ``group_norm.hip`` serves: bf16 ``[B, P, C]`` on 16-byte-aligned storage, ``C % 8 == 0``, 8 or 16 channels
+    per group, at most 5 levels (the entry points' own rule, mirrored so that a caller can decide before allocating)."""
+    C = x.shape[-1]
+    return (x.dtype == torch.bfloat16 and 1 <= nlev <= MAXLEV and C % 8 == 0 and groups >= 1 and C % groups == 0
+            and C // groups in (8, 16) and x.data_ptr() % 16 == 0)
+
+
+def gn_relu_fwd(x, shapes, gamma, beta, groups, eps=1e-5):
+    """``relu(group_norm(x))`` per (image, level, group) of the packed ``[B, P, C]`` bf16 pyramid: returns
+    (y like x, mean, rstd f32 ``[B, L, G]``); raises :class:`NotServed` for what the kernels do not serve (channels per
+    group other than 8 or 16, ``C % 8``, more than 5 levels, activations that are not bf16)."""
+    if x.dim() != 3 or gamma.numel() != x.shape[2] or beta.numel() != x.shape[2]:
+        raise ValueError("gn_relu_fwd: x [B, P, C] and gamma / beta [C] expected")
+    B, P, C = x.shape
+    lev, npix = _gn_levels(shapes)
+    if sum(npix) != P:
+        raise ValueError("gn_relu_fwd: {} rows do not match the levels {}".format(P, tuple(shapes)))
+    x = x.contiguous()
+    L, G = len(npix), int(groups)
+    if not gn_served(x, G, L):
+        raise NotServed("gn_relu_fwd")      # decided before anything is allocated (the entry point judges again)
+    y = torch.empty_like(x)
+    mean = torch.empty((B, L, max(G, 1)), dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    part = torch.empty(max(1, 2 * _gn_blocks(B, npix) * max(G, 1)), dtype=torch.float32, device=x.device)
+    rc = lib().mxr_gn_relu_fwd(_p(x), _p(gamma.detach().float().contiguous()), _p(beta.detach().float().contiguous()),
+                               _p(y), _p(mean), _p(rstd), _p(part), part.numel(), B, P, C, G, float(eps), L, lev,
+                               _gn_dt(x), _s())
+    if rc == -1:
+        raise NotServed("gn_relu_fwd")
+    _chk(rc, "gn_relu_fwd")
+    return y, mean, rstd
+
+
+def gn_relu_bwd(dy, x, shapes, gamma, beta, mean, rstd, groups):
+    """Backward of :func:`gn_relu_fwd` (the ReLU mask recomputed from ``x``): (dx like x, dgamma, dbeta f32 [C])."""
+    B, P, C = x.shape
+    lev, npix = _gn_levels(shapes)
+    L, G = len(npix), int(groups)
+    if x.dim() != 3 or tuple(dy.shape) != tuple(x.shape) or sum(npix) != P:
+        raise ValueError("gn_relu_bwd: dy and x [B, P, C] with P the levels' pixels expected")
+    if gamma.numel() != C or beta.numel() != C or mean.numel() != B * L * G or rstd.numel() != B * L * G:
+        raise ValueError("gn_relu_bwd: gamma / beta [C] and mean / rstd [B, L, G] expected")
+    x = x.contiguous()
+    gamma, beta, mean, rstd = (t.detach().float().contiguous() for t in (gamma, beta, mean, rstd))
+    if not gn_served(x, G, L):
+        raise NotServed("gn_relu_bwd")
+    dy = dy.to(x.dtype).contiguous()
+    dx = torch.empty_like(x)
+    dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty_like(dgamma)
+    work = torch.empty(2 * _gn_blocks(B, npix) * (G + C) + 2 * B * L * G, dtype=torch.float32, device=x.device)
+    rc = lib().mxr_gn_relu_bwd(_p(dy), _p(x), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dx), _p(dgamma), _p(dbeta),
+                               _p(work), work.numel(), B, P, C, G, L, lev, _gn_dt(x), _s())
+    if rc == -1:
+        raise NotServed("gn_relu_bwd")
+    _chk(rc, "gn_relu_bwd")
+    return dx, dgamma, dbeta
+
+
+class GroupNormReluPackedFn(torch.autograd.Function):
+    """Fused GroupNorm + ReLU of the packed pyramid; saves x, mean and rstd (no mask, no normalised copy)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, shapes, groups, eps):
+        x = x.contiguous()
+        g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+        y, mean, rstd = gn_relu_fwd(x, shapes, g32, b32, groups, eps)
+        ctx.save_for_backward(x, mean, rstd, g32, b32)
+        ctx.cfg = (tuple(shapes), groups, gamma.dtype, beta.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean, rstd, g32, b32 = ctx.saved_tensors
+        shapes, groups, gdt, bdt = ctx.cfg
+        dx, dgamma, dbeta = gn_relu_bwd(dy, x, shapes, g32, b32, mean, rstd, groups)
+        return dx, dgamma.to(gdt), dbeta.to(bdt), None, None, None
 
 
 # =========================================================================================

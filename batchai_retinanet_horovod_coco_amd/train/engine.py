@@ -66,6 +66,11 @@ class Trainer:
                 raise ValueError("classification_loss={!r} does not go with fp8: the classification final's focal loss "
                                  "is part of the fp8 epilogue".format(classification_loss))
         self.classification_loss = classification_loss
+        if getattr(model, "head_norm", None) is not None:
+            from ..ops import fp8 as _fp8
+            if _fp8.enabled():
+                raise ValueError("head_norm={!r} does not go with fp8: the fp8 tower layers hand fp8 copies of their "
+                                 "ReLU outputs to each other".format(model.head_norm))
         if assigner not in ("iou", "atss"):
             raise ValueError("assigner must be 'iou' or 'atss', got {!r}".format(assigner))
         if assigner == "iou" and atss_topk != anchor_ops.ATSS_TOPK:
@@ -204,6 +209,10 @@ class Trainer:
         """The fused classification loss kernel of this trainer: (loss, d loss / d logits)."""
         from ..ops import native
         cls = out["classification"]
+        if getattr(self.model, "head_norm", None) is not None:
+            from ..ops import fp8 as _fp8
+            if _fp8.enabled():      # switched on after the constructor's check
+                raise RuntimeError("head_norm={!r} does not go with fp8".format(self.model.head_norm))
         if self.classification_loss == "focal":
             return native.focal_fwd_bwd(cls, state, label, npos, **pad)
         from ..ops import fp8 as _fp8
