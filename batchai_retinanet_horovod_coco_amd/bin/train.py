@@ -8,7 +8,7 @@ Same subcommands, flags, defaults and argument checks as ``/root/reference/train
 ``--no-evaluation``, ``--freeze-backbone``, ``--random-transform``, ``--image-min-side``,
 ``--image-max-side``), plus a ``synthetic`` dataset and MI355X options (``--dtype``, ``--clip-mode``,
 ``--bucket-mb``, ``--allreduce-dtype``, ``--workers``, ``--shard-data``, ``--checkpoint-format``,
-``--lr``, ``--clipnorm``, ``--optimizer``, ``--momentum``, ``--nesterov``, ``--weight-decay``, ``--ema-decay``, ``--weights-ema``, ``--regression-loss``, ``--regression-weight``, ``--classification-loss``, ``--head-norm``, ``--head-norm-groups``, ``--warmup-epochs``, ``--seed``, ``--log-every``, ``--no-metric-average``, ``--log-all-ranks``,
+``--lr``, ``--clipnorm``, ``--optimizer``, ``--momentum``, ``--nesterov``, ``--weight-decay``, ``--ema-decay``, ``--weights-ema``, ``--regression-loss``, ``--regression-weight``, ``--classification-loss``, ``--head-norm``, ``--head-norm-groups``, ``--regression-bins``, ``--regression-range``, ``--dfl-weight``, ``--warmup-epochs``, ``--seed``, ``--log-every``, ``--no-metric-average``, ``--log-all-ranks``,
 ``--metrics-jsonl``, ``--stop-on-nan``, ``--graph``, ``--graph-shapes``, ``--eval-batch-size``,
 ``--eval-pad-multiple``, ``--eval-workers``).
 
@@ -59,6 +59,7 @@ def check_args(parsed_args):
     resolve_assigner(parsed_args)
     resolve_classification_loss(parsed_args)
     resolve_head_norm(parsed_args)
+    resolve_regression_bins(parsed_args)
     if getattr(parsed_args, "warmup_epochs", 0) < 0:
         raise SystemExit("--warmup-epochs must be >= 0")
     if not 0.0 <= getattr(parsed_args, "ema_decay", 0.0) < 1.0:
@@ -190,6 +191,56 @@ def head_norm_kwargs(parsed_args):
     if getattr(parsed_args, "head_norm", None) != "gn":
         return {}
     return dict(head_norm="gn", head_norm_groups=parsed_args.head_norm_groups)
+
+
+def resolve_regression_bins(parsed_args):
+    """``--regression-bins`` / ``--regression-range`` / ``--dfl-weight`` when given, else what ``--snapshot`` stores,
+    else the plain 4-number head.  A flag that differs from the snapshot wins, with a warning: every layer but the
+    regression final is loaded.  ``regression_bins_override`` tells whether the snapshot's model is rebuilt with the
+    flags."""
+    if not hasattr(parsed_args, "regression_bins"):
+        return parsed_args
+    given, given_r, given_w = parsed_args.regression_bins, parsed_args.regression_range, parsed_args.dfl_weight
+    stored, stored_r, stored_w, have = 0, 8.0, 0.25, False
+    if parsed_args.snapshot and os.path.exists(parsed_args.snapshot):
+        from ..io import checkpoint
+        stored, stored_r = checkpoint.stored_regression_bins(parsed_args.snapshot)
+        stored_w = checkpoint.stored_dfl_weight(parsed_args.snapshot)
+        have = True
+    bins = stored if given is None else given
+    if bins != 0 and not 2 <= bins <= 32:
+        raise SystemExit("--regression-bins must be 0 (off) or 2..32, got {}".format(bins))
+    if have and bins != stored:
+        warnings.warn("--regression-bins {} differs from --snapshot {}, whose model was built with {}: training on "
+                      "with {}".format(bins, parsed_args.snapshot, stored, bins))
+    if not bins:
+        if given_r is not None:
+            raise SystemExit("--regression-range goes with --regression-bins; a 4-number box head has no bins")
+        if given_w is not None:
+            raise SystemExit("--dfl-weight goes with --regression-bins; a 4-number box head has no distribution loss")
+    rng = given_r if given_r is not None else (stored_r if stored else 8.0)
+    weight = given_w if given_w is not None else (stored_w if stored else 0.25)
+    if bins:
+        if not rng > 0:
+            raise SystemExit("--regression-range must be > 0, got {}".format(rng))
+        if not weight >= 0:
+            raise SystemExit("--dfl-weight must be >= 0, got {}".format(weight))
+        if have and stored and bins == stored and rng != stored_r:
+            warnings.warn("--regression-range {} differs from --snapshot {}, whose model was built with {}: training "
+                          "on with {}".format(rng, parsed_args.snapshot, stored_r, rng))
+        if getattr(parsed_args, "dtype", None) == "fp8":
+            raise SystemExit("--regression-bins {} cannot be combined with --dtype fp8: the regression final's {} "
+                             "outputs would run in fp8".format(bins, 9 * 4 * bins))
+    parsed_args.regression_bins_override = have and (bins != stored or (bins and rng != stored_r))
+    parsed_args.regression_bins, parsed_args.regression_range, parsed_args.dfl_weight = bins, rng, weight
+    return parsed_args
+
+
+def regression_bins_kwargs(parsed_args):
+    """The model keywords of the resolved ``--regression-bins`` (none for the 4-number head)."""
+    if not getattr(parsed_args, "regression_bins", 0):
+        return {}
+    return dict(regression_bins=parsed_args.regression_bins, regression_range=parsed_args.regression_range)
 
 
 def resolve_assigner(parsed_args):
@@ -351,6 +402,19 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--head-norm-groups", type=int, default=None, metavar="G",
                         help="With --head-norm gn: groups of the 256 tower channels (default 32, or what --snapshot "
                              "stores; must divide 256).")
+    parser.add_argument("--regression-bins", type=int, default=None, metavar="K",
+                        help="Distribution box head of Generalized Focal Loss: the regression final emits K logits "
+                             "per box side, the delta is the expectation over K bins from -R to +R (--regression-range) "
+                             "and Distribution Focal Loss trains the two bins around the target, in fused kernels.  0 "
+                             "(default): the 4-number head.  2..32; GFL's value is 17.  Not with --dtype fp8.  With "
+                             "--snapshot the stored model's setting is used unless this flag is given; the flag wins, "
+                             "with a warning.")
+    parser.add_argument("--regression-range", type=float, default=None, metavar="R",
+                        help="With --regression-bins: the bins span -R..+R in the head's delta units (default 8, or "
+                             "what --snapshot stores).")
+    parser.add_argument("--dfl-weight", type=float, default=None, metavar="W",
+                        help="With --regression-bins: weight of the Distribution Focal Loss (default 0.25, or what "
+                             "--snapshot stores).")
     parser.add_argument("--assigner", choices=["iou", "atss"], default=None,
                         help="Anchor target assignment.  iou (default): the reference's fixed thresholds (IoU >= 0.5 "
                              "positive, 0.4-0.5 ignored).  atss: adaptive training sample selection -- every box takes "
@@ -596,7 +660,10 @@ def main(args=None):
         print("Loading model, this may take a second...")
         model = models.load_model(args.snapshot, backbone_name=args.backbone,
                                   **(dict(head_norm=args.head_norm, head_norm_groups=args.head_norm_groups)
-                                     if args.head_norm_override else {}))
+                                     if args.head_norm_override else {}),
+                                  **(dict(regression_bins=args.regression_bins,
+                                          regression_range=args.regression_range)
+                                     if args.regression_bins_override else {}))
     else:
         weights = args.weights
         if weights is None and args.imagenet_weights:
@@ -604,7 +671,7 @@ def main(args=None):
         print("Creating model, this may take a second...")
         model = backbone.retinanet(train_generator.num_classes(),
                                    modifier=models.freeze if args.freeze_backbone else None,
-                                   **head_norm_kwargs(args))
+                                   **head_norm_kwargs(args), **regression_bins_kwargs(args))
         if weights is not None:
             checkpoint.load_weights(model, weights, by_name=True, skip_mismatch=True,
                                     **(dict(group="ema_weights") if args.weights_ema else {}))
@@ -635,6 +702,7 @@ def main(args=None):
                       **(dict(assigner="atss", atss_topk=args.atss_topk) if args.assigner == "atss" else {}),
                       **(dict(classification_loss=args.classification_loss)
                          if args.classification_loss != "focal" else {}),
+                      **(dict(dfl_weight=args.dfl_weight) if args.regression_bins else {}),
                       **(dict(optimizer="sgd", momentum=args.momentum, nesterov=args.nesterov,
                               weight_decay=args.weight_decay) if args.optimizer == "sgd" else {}))
     if args.snapshot is not None:

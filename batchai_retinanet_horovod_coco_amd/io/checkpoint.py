@@ -100,7 +100,32 @@ def model_config(model) -> Dict:
         # only with the norm on: a default model's config stays what it was
         cfg["config"]["head_norm"] = model.head_norm
         cfg["config"]["head_norm_groups"] = int(model.head_norm_groups)
+    if getattr(model, "regression_bins", 0):
+        # likewise the distribution box head
+        cfg["config"]["regression_bins"] = int(model.regression_bins)
+        cfg["config"]["regression_range"] = float(model.regression_range)
     return cfg
+
+
+# the regression final, the one layer a distribution box head (regression_bins) changes the shape of: its Keras
+# weights and its state_dict tensors
+_REG_FINAL = re.compile(r"(^|/)pyramid_regression/(kernel|bias):0$|^regression_submodel\.final\.(weight|bias)$")
+
+
+def stored_regression_bins(path: str) -> Tuple[int, float]:
+    """(regression_bins, regression_range) of the model a checkpoint holds: (0, 8.0) for a plain 4-number head."""
+    cfg = read_model_config(path).get("config", {})
+    return int(cfg.get("regression_bins", 0)), float(cfg.get("regression_range", 8.0))
+
+
+def _bins_differ(path: str, model) -> bool:
+    """Whether the model was built with other ``regression_bins`` than the model the file holds."""
+    return stored_regression_bins(path)[0] != int(getattr(model, "regression_bins", 0) or 0)
+
+
+def stored_dfl_weight(path: str) -> float:
+    """The DFL weight a checkpoint was trained with (0.25 unless the file says otherwise)."""
+    return float((_stored_training_config(path) or {}).get("dfl_weight", 0.25))
 
 
 def stored_head_norm(path: str) -> Tuple[Optional[str], int]:
@@ -199,6 +224,8 @@ def training_config(optimizer) -> Dict:
         out["assigner"] = optimizer.assigner
         if getattr(optimizer, "atss_topk", 9) != 9:
             out["atss_topk"] = int(optimizer.atss_topk)
+    if getattr(optimizer, "dfl_weight", 0.25) != 0.25:
+        out["dfl_weight"] = float(optimizer.dfl_weight)
     return out
 
 
@@ -372,14 +399,18 @@ def has_ema_weights(path: str) -> bool:
 
 
 def load_weights(model, path: str, by_name: bool = True, skip_mismatch: bool = False,
-                 group: str = "model_weights", strict_head_norm: bool = True) -> List[str]:
+                 group: str = "model_weights", strict_head_norm: bool = True,
+                 skip_regression_final: bool = False) -> List[str]:
     """Keras ``load_weights`` (HDF5 or safetensors).  Returns the list of skipped weights.  ``group="ema_weights"``
-    loads the averaged set a run with a weight EMA stored; a ValueError when the file has none."""
+    loads the averaged set a run with a weight EMA stored; a ValueError when the file has none.
+    ``skip_regression_final``: the regression final's kernel and bias stay at their initial values where the file's
+    have another shape (a model built with other ``regression_bins`` than the file's)."""
     if group not in ("model_weights", EMA_GROUP):
         raise ValueError("group must be 'model_weights' or '{}', got {!r}".format(EMA_GROUP, group))
     if path.endswith(".safetensors"):
         return load_safetensors(model, path, optimizer=None, skip_mismatch=skip_mismatch,
-                                prefix=EMA_PREFIX if group == EMA_GROUP else "", strict_head_norm=strict_head_norm)[1]
+                                prefix=EMA_PREFIX if group == EMA_GROUP else "", strict_head_norm=strict_head_norm,
+                                skip_regression_final=skip_regression_final)[1]
     f = hdf5.File(path, "r")
     file_layers = _layer_weights_from_file(f, group)
     layers = keras_layers(model)
@@ -408,7 +439,7 @@ def load_weights(model, path: str, by_name: bool = True, skip_mismatch: bool = F
             for (wname, t, kind), (fname, arr) in zip(ws, fws):
                 a = _from_keras(arr, kind)
                 if tuple(a.shape) != tuple(t.shape):
-                    if skip_mismatch:
+                    if skip_mismatch or (skip_regression_final and _REG_FINAL.search(wname)):
                         skipped.append(wname)
                         continue
                     raise ValueError("Layer '{}' weight shape {} does not match saved shape {}".format(
@@ -490,7 +521,8 @@ def checkpoint_epoch(path: str) -> Optional[int]:
 
 def load_model(filepath: str, backbone_name: str = "resnet50", **kwargs):
     """``models.load_model``: rebuild the architecture from the stored config, load weights.  ``head_norm`` /
-    ``head_norm_groups`` given here win over the stored ones (the weights they have in common are loaded)."""
+    ``head_norm_groups`` and ``regression_bins`` / ``regression_range`` given here win over the stored ones (the
+    weights they have in common are loaded)."""
     from .. import models
     cfg = read_model_config(filepath).get("config", {})
     name = cfg.get("backbone", backbone_name)
@@ -499,9 +531,24 @@ def load_model(filepath: str, backbone_name: str = "resnet50", **kwargs):
     if head_norm not in (None, "none"):
         norm = dict(head_norm=head_norm,
                     head_norm_groups=int(kwargs.get("head_norm_groups") or cfg.get("head_norm_groups", 32)))
+    # likewise ``regression_bins`` / ``regression_range``: every layer but the regression final is shared
+    stored_bins = int(cfg.get("regression_bins", 0))
+    bins = int(kwargs["regression_bins"]) if kwargs.get("regression_bins") is not None else stored_bins
+    if bins:
+        rng = kwargs.get("regression_range")
+        norm.update(regression_bins=bins,
+                    regression_range=float(rng if rng is not None else cfg.get("regression_range", 8.0)))
     model = models.backbone(name).retinanet(int(cfg.get("num_classes", kwargs.get("num_classes", 80))), **norm)
-    load_weights(model, filepath, by_name=True, skip_mismatch=False, strict_head_norm="head_norm" not in kwargs)
+    if bins != stored_bins:
+        warnings.warn("{} holds a regression final for {}, the model is built with {}: that layer stays at its initial "
+                      "values, every other layer is loaded".format(filepath, _bins_name(stored_bins), _bins_name(bins)))
+    load_weights(model, filepath, by_name=True, skip_mismatch=False, strict_head_norm="head_norm" not in kwargs,
+                 skip_regression_final=bins != stored_bins)
     return model
+
+
+def _bins_name(bins: int) -> str:
+    return "{} bins per box side".format(bins) if bins else "4 numbers per box"
 
 
 # ------------------------------------------------------------------------------ safetensors
@@ -537,9 +584,10 @@ def save_safetensors(path: str, model, optimizer=None, epoch: Optional[int] = No
 
 
 def load_safetensors(model, path: str, optimizer=None, skip_mismatch: bool = False, prefix: str = "",
-                     strict_head_norm: Optional[bool] = True):
+                     strict_head_norm: Optional[bool] = True, skip_regression_final: bool = False):
     """Returns (metadata, skipped tensors); ``metadata["optimizer_restored"]`` tells whether the optimizer state was
-    restored (only from a file written with the live optimizer's class).  ``prefix="ema/"`` loads the averaged set."""
+    restored (only from a file written with the live optimizer's class).  ``prefix="ema/"`` loads the averaged set.
+    ``skip_regression_final``: as in :func:`load_weights`."""
     from safetensors.torch import load_file
     from safetensors import safe_open
     sd = load_file(path)
@@ -559,7 +607,7 @@ def load_safetensors(model, path: str, optimizer=None, skip_mismatch: bool = Fal
             if not file_has_gn and _GN_TENSOR.search(k):
                 continue            # stays at its initial value (_check_head_norm)
             if k not in sd or tuple(sd[k].shape) != tuple(v.shape):
-                if skip_mismatch:
+                if skip_mismatch or (skip_regression_final and k in sd and _REG_FINAL.search(k)):
                     skipped.append(k)
                     continue
                 raise ValueError("missing or mismatched tensor {}".format(k))
@@ -575,6 +623,11 @@ def load_safetensors(model, path: str, optimizer=None, skip_mismatch: bool = Fal
                 if "lr" in meta:
                     optimizer.lr = float(meta["lr"])
                 restored = True
+            elif skip_regression_final and all(k in sd for k in keys):
+                # the flat state of a model with another regression final: no slot of it lines up with this one's
+                warnings.warn("{} holds optimizer state for another list of trainable parameters than the model's: "
+                              "weights loaded, optimizer state left fresh".format(path))
+            if restored:
                 if _ema_of(optimizer) is not None:
                     params = dict(model.named_parameters())
                     if all(EMA_PREFIX + k in sd for k in params) and "ema_updates" in meta:
@@ -601,7 +654,8 @@ def load_optimizer(model, optimizer, path: str) -> bool:
     (a safetensors file's weights are read again on the way)."""
     if path.endswith(".safetensors"):
         # (the second read of a file whose weights load_weights has judged: no second head_norm warning)
-        return bool(load_safetensors(model, path, optimizer, strict_head_norm=None)[0]["optimizer_restored"])
+        return bool(load_safetensors(model, path, optimizer, strict_head_norm=None,
+                                     skip_regression_final=_bins_differ(path, model))[0]["optimizer_restored"])
     return load_optimizer_h5(model, optimizer, path)
 
 

@@ -146,14 +146,18 @@ class Submodel(nn.Module):
 
 
 class RetinaNet(nn.Module):
-    """Training model.  ``forward(images NHWC) -> {'regression', 'classification'}``."""
+    """Training model.  ``forward(images NHWC) -> {'regression', 'classification'}``; with ``regression_bins``
+    also ``'regression_logits'``."""
 
     def __init__(self, num_classes: int, backbone: str = "resnet50", num_anchors: int = 9,
                  feature_size: int = 256, prior_probability: float = 0.01, head_norm: Optional[str] = None,
-                 head_norm_groups: int = 32):
+                 head_norm_groups: int = 32, regression_bins: int = 0, regression_range: float = 8.0):
         super().__init__()
         self.head_norm = check_head_norm(head_norm, head_norm_groups)
         self.head_norm_groups = int(head_norm_groups)
+        # regression_bins K > 0: the regression final emits K logits per box side (channel a * 4K + s * K + i) and
+        # the deltas are the expectation over the bins -regression_range .. +regression_range (ops.boxes.box_integral)
+        self.regression_bins, self.regression_range = box_ops.check_regression_bins(regression_bins, regression_range)
         self.num_classes = num_classes
         self.num_anchors = num_anchors
         self.backbone_name = backbone
@@ -165,7 +169,8 @@ class RetinaNet(nn.Module):
         c3, c4, c5 = self.backbone.out_channels[1:]
         self.fpn = FPN(c3, c4, c5, feature_size)
         self.regression_submodel = Submodel("regression_submodel", "pyramid_regression", feature_size, 256,
-                                            num_anchors * 4, 0.0, self.head_norm, self.head_norm_groups)
+                                            num_anchors * 4 * max(1, self.regression_bins), 0.0, self.head_norm,
+                                            self.head_norm_groups)
         self.classification_submodel = Submodel("classification_submodel", "pyramid_classification", feature_size,
                                                 256, num_anchors * num_classes,
                                                 prior_probability_bias(prior_probability), self.head_norm,
@@ -220,13 +225,36 @@ class RetinaNet(nn.Module):
                 # (ops.conv_launch.FocalRequest)
                 self.cls_pad_sink["focal"] = req
             cls = self.classification_submodel.forward_packed(packed, shapes, self.cls_pad_sink, join=join)
-            return {"regression": reg.reshape(B, -1, 4), "classification": cls.reshape(B, -1, self.num_classes)}
+            cls = cls.reshape(B, -1, self.num_classes)
+            if self.regression_bins:
+                return self._with_integral(reg.reshape(B, -1, 4 * self.regression_bins), cls)
+            return {"regression": reg.reshape(B, -1, 4), "classification": cls}
         self.cls_pad_sink = self.reg_pad_sink = None
         reg = self.regression_submodel(feats)
         cls = self.classification_submodel(feats)
-        regression = torch.cat([r.reshape(B, -1, 4) for r in reg], dim=1)
         classification = torch.cat([c.reshape(B, -1, self.num_classes) for c in cls], dim=1)
+        if self.regression_bins:
+            return self._with_integral(torch.cat([r.reshape(B, -1, 4 * self.regression_bins) for r in reg], dim=1),
+                                       classification)
+        regression = torch.cat([r.reshape(B, -1, 4) for r in reg], dim=1)
         return {"regression": regression, "classification": classification}
+
+    def _with_integral(self, logits: torch.Tensor, classification: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """The outputs of a distribution head: ``regression_logits`` (B, A, 4K) and their integral ``regression``
+        (B, A, 4).  ``integral_request`` (the Trainer's anchor states for this forward, like ``focal_request``): the
+        fused loss path reads the deltas of positive rows only and computes the integral's backward itself, so the
+        kernel's training form runs -- positive rows only, the others 0, no gradient -- instead of every row."""
+        K, R = self.regression_bins, self.regression_range
+        state = getattr(self, "integral_request", None)
+        if state is not None and logits.is_cuda:
+            from ..ops import native
+            try:
+                regression = native.box_integral_fwd(logits.detach(), K, R, state=state)
+                return {"regression": regression, "regression_logits": logits, "classification": classification}
+            except native.NotServed:
+                pass    # the differentiable expression below; the Trainer sees that it requires grad
+        return {"regression": box_ops.box_integral(logits, K, R), "regression_logits": logits,
+                "classification": classification}
 
     # ------------------------------------------------------------------ helpers
     def convs(self) -> List[Conv2D]:

@@ -8,6 +8,7 @@ kernels in ``csrc/kernels/detect.hip`` (decode+clip, bitmask NMS) are dispatched
 """
 from __future__ import annotations
 
+import warnings
 from typing import Optional, Tuple
 
 import torch
@@ -25,6 +26,56 @@ def bbox_transform_inv(anchors: torch.Tensor, deltas: torch.Tensor, mean=BOX_MEA
     x2 = anchors[..., 2] + d[..., 2] * aw
     y2 = anchors[..., 3] + d[..., 3] * ah
     return torch.stack([x1, y1, x2, y2], dim=-1)
+
+
+MAX_REGRESSION_BINS = 32
+_FALLBACK_WARNED = set()
+
+
+def check_regression_bins(bins, rng: float = 8.0):
+    """``(bins, range)`` as the model keeps them: 0 bins (the plain 4-number head) or 2..32 with a range > 0."""
+    bins = int(bins or 0)
+    if bins != 0 and not 2 <= bins <= MAX_REGRESSION_BINS:
+        raise ValueError("regression_bins must be 0 or 2..{}, got {}".format(MAX_REGRESSION_BINS, bins))
+    if not float(rng) > 0:
+        raise ValueError("regression_range must be > 0, got {}".format(rng))
+    return bins, float(rng)
+
+
+def box_bins(K: int, R: float, dtype=torch.float32, device=None) -> torch.Tensor:
+    """The K bin values ``v_i = -R + i * D``, ``D = 2R / (K - 1)``, in the head's delta units."""
+    return (-R + torch.arange(K, dtype=torch.float64, device=device) * (2.0 * R / (K - 1))).to(dtype)
+
+
+def _box_integral_torch(logits: torch.Tensor, K: int, R: float) -> torch.Tensor:
+    dt = logits.dtype if logits.dtype == torch.float64 else torch.float32
+    l = logits.to(dt).reshape(logits.shape[:-1] + (4, K))
+    p = torch.softmax(l, dim=-1)                     # subtracts the maximum
+    return (p * box_bins(K, R, dt, logits.device)).sum(-1).to(logits.dtype)
+
+
+def box_integral(logits: torch.Tensor, K: int, R: float = 8.0, backend: str = "auto") -> torch.Tensor:
+    """The deltas of a distribution box head (Generalized Focal Loss, section 3.2): logits (..., 4 * K), per side a
+    softmax over K bins, out (..., 4) the expectations ``sum_i p_i v_i`` in the logits' dtype (fp32 arithmetic and one
+    rounding; float64 logits compute in float64: the kernel's oracle).  On the GPU every row runs in
+    ``box_dist.hip``; what it does not serve runs as this torch expression with one warning per form."""
+    from . import native
+    K = int(K)
+    if K < 2 or logits.shape[-1] != 4 * K:
+        raise ValueError("box_integral: logits (..., 4 * K) with K >= 2 expected, got {} with K = {}".format(
+            tuple(logits.shape), K))
+    if backend == "auto":
+        backend = "hip" if (logits.is_cuda and native.available()) else "torch"
+    if backend == "hip":
+        try:
+            return native.BoxIntegralFn.apply(logits, K, float(R))
+        except native.NotServed:
+            key = ("integral", K, logits.dtype)
+            if key not in _FALLBACK_WARNED:
+                _FALLBACK_WARNED.add(key)
+                warnings.warn("box_dist.hip does not serve {} bins of {}: the box integral runs as the torch "
+                              "expression".format(K, logits.dtype))
+    return _box_integral_torch(logits, K, float(R))
 
 
 def clip_boxes(boxes: torch.Tensor, height: float, width: float) -> torch.Tensor:

@@ -17,10 +17,13 @@ Behavioural spec: keras-retinanet ``losses.focal(alpha=0.25, gamma=2.0)`` and
 * ``quality_loss`` (Quality Focal / Varifocal loss, ``Trainer(classification_loss=...)``) takes focal's place on
   request: the label class of a positive anchor is trained towards ``quality_targets``, the IoU of its predicted box.
   The torch expression here is the CPU path and, in float64, the oracle of ``csrc/kernels/quality_loss.hip``.
+* ``distribution_focal_loss`` (``RetinaNet(regression_bins=K)``) trains a distribution box head next to the box loss on
+  its integral deltas (``ops.boxes.box_integral``); the kernel is ``csrc/kernels/box_dist.hip``.
 """
 from __future__ import annotations
 
 import math
+import warnings
 from typing import Optional
 
 import torch
@@ -220,6 +223,54 @@ def quality_loss(logits: torch.Tensor, reg: torch.Tensor, reg_t: torch.Tensor, s
     if backend == "hip":
         return native.QualityLossFn.apply(logits, reg, reg_t, state, label, anchors, kind)
     return _quality_torch(logits, reg, reg_t, state, label, anchors, kind)
+
+
+DFL_WEIGHT = 0.25
+DFL_CLAMP_MARGIN = 0.01
+_FALLBACK_WARNED = set()
+
+
+def _dfl_torch(logits, reg_t, state, K, R, weight):
+    dt = logits.dtype if logits.dtype == torch.float64 else torch.float32
+    l = logits.to(dt).reshape(-1, 4, K)
+    pos = (state == 1).reshape(-1)
+    D = 2.0 * R / (K - 1)
+    u = ((reg_t.to(dt).reshape(-1, 4) + R) / D).clamp(0, (K - 1) - DFL_CLAMP_MARGIN)
+    il = u.floor()
+    wr = u - il
+    wl = 1 - wr
+    il = il.long()
+    logp = torch.log_softmax(l, dim=-1)              # no log of a rounded probability
+    per = -(wl * logp.gather(-1, il[..., None])[..., 0] + wr * logp.gather(-1, il[..., None] + 1)[..., 0])
+    s = (per * pos[:, None].to(dt)).sum()
+    return weight * s / (4 * torch.clamp(pos.sum().to(dt), min=1.0))
+
+
+def distribution_focal_loss(logits: torch.Tensor, reg_t: torch.Tensor, state: torch.Tensor, K: int, R: float = 8.0,
+                            weight: float = DFL_WEIGHT, backend: str = "auto") -> torch.Tensor:
+    """``weight`` x Distribution Focal Loss (Li et al. 2020, section 3.3) of a distribution box head: logits
+    (B, A, 4 * K), per side K bins ``ops.boxes.box_bins(K, R)``; the target delta ``reg_t`` (B, A, 4) is clamped into the
+    bins' range (0.01 of a bin below the last value) and the two bins that bracket it are trained towards it with the
+    weights of a linear interpolation, on the log-softmax.  Summed over the sides of the rows with state 1 and divided
+    by 4 max(1, #positives): no weighting by the quality score.  The torch expression computes in fp32, or in float64
+    when the logits are float64 (the kernel's oracle)."""
+    from . import native
+    K = int(K)
+    if K < 2 or logits.shape[-1] != 4 * K:
+        raise ValueError("distribution_focal_loss: logits (..., 4 * K) with K >= 2 expected, got {} with K = {}".format(
+            tuple(logits.shape), K))
+    if backend == "auto":
+        backend = "hip" if (logits.is_cuda and native.available()) else "torch"
+    if backend == "hip":
+        try:
+            return native.DistributionFocalLossFn.apply(logits, reg_t, state, K, float(R), float(weight))
+        except native.NotServed:
+            key = ("dfl", K, logits.dtype)
+            if key not in _FALLBACK_WARNED:
+                _FALLBACK_WARNED.add(key)
+                warnings.warn("box_dist.hip does not serve {} bins of {}: the distribution focal loss runs as the torch "
+                              "expression".format(K, logits.dtype))
+    return _dfl_torch(logits, reg_t, state, K, float(R), float(weight))
 
 
 def focal_loss(logits: torch.Tensor, state: torch.Tensor, label: torch.Tensor,

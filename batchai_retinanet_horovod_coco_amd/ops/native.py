@@ -49,6 +49,9 @@ _SIGS = {
                              c_int, c_vp],
     "mxr_quality_loss_fwd_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_int, c_int,
                                  c_int, c_int, c_int, c_vp],
+    "mxr_box_integral_fwd": [c_vp, c_vp, c_vp, c_ll, c_int, c_float, c_int, c_vp],
+    "mxr_box_dist_fwd_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_float, c_float, c_int, c_int,
+                             c_int, c_vp],
     "mxr_loss_grid": [],
     "mxr_gn_chunk_rows": [],
     "mxr_gn_relu_fwd": [c_vp] * 7 + [c_ll, c_int, c_ll, c_int, c_int, c_float, c_int, ctypes.POINTER(c_int), c_int, c_vp],
@@ -422,6 +425,115 @@ def quality_loss_fwd_bwd(logits, reg, reg_t, anchors, state, label, npos=None, k
                                         _p(out), rows, C, A, CLS_KINDS[kind], _dt(logits), int(group) if ld else 0, ld,
                                         _s()), "quality_loss")
     return out.reshape(()), grad
+
+
+def _dist_dt(t: torch.Tensor) -> int:
+    return {torch.float32: 0, torch.bfloat16: 1}.get(t.dtype, 2)
+
+
+def box_integral_fwd(logits, K, R, state=None):
+    """The expectation of the per-side bin distributions (``box_dist.hip``): logits (..., 4 * K) -> deltas (..., 4) in
+    the logits' dtype.  ``state`` (one int8 per row): only rows with state 1 read their logits, every other row's
+    deltas are 0 (the training form).  Raises :class:`NotServed` for what the kernel does not serve (K outside
+    2..32, a dtype other than bf16 / fp32)."""
+    K = int(K)
+    if K < 1 or logits.shape[-1] != 4 * K:
+        raise ValueError("box_integral_fwd: logits (..., 4 * K) expected, got {} with K = {}".format(
+            tuple(logits.shape), K))
+    logits = logits.contiguous()
+    rows = logits.numel() // (4 * K)
+    if state is not None:
+        if state.numel() != rows or state.dtype != torch.int8:
+            raise ValueError("box_integral_fwd: state (rows,) int8 expected")
+        state = state.contiguous()
+    if not 2 <= K <= 32 or _dist_dt(logits) == 2:
+        raise NotServed("box_integral_fwd")     # decided before anything is allocated (the entry point judges again)
+    out = torch.empty(logits.shape[:-1] + (4,), dtype=logits.dtype, device=logits.device)
+    rc = lib().mxr_box_integral_fwd(_p(logits), _p(state), _p(out), rows, K, float(R), _dist_dt(logits), _s())
+    if rc == -1:
+        raise NotServed("box_integral_fwd")
+    _chk(rc, "box_integral_fwd")
+    return out
+
+
+def box_dist_fwd_bwd(logits, dreg, reg_t, state, npos=None, K=17, R=8.0, weight=0.25, grad_out=None, group=0):
+    """Distribution Focal Loss plus the backward of the integral in one launch (``box_dist.hip``): returns
+    (loss 0-d f32 = weight x DFL / (4 max(1, npos)), dlogits = integral backward of ``dreg`` + DFL gradient).
+    logits (..., 4 * K); ``dreg`` the box loss's gradient w.r.t. the deltas, (..., 4) of the logits' dtype in the plain
+    layout; ``grad_out`` / ``group``: as in :func:`smooth_l1_fwd_bwd`, rows of ``group`` anchors x 4K values.  Raises
+    :class:`NotServed` like :func:`box_integral_fwd`."""
+    K = int(K)
+    if K < 1 or logits.shape[-1] != 4 * K:
+        raise ValueError("box_dist_fwd_bwd: logits (..., 4 * K) expected, got {} with K = {}".format(
+            tuple(logits.shape), K))
+    logits = logits.contiguous()
+    rows = logits.numel() // (4 * K)
+    if not (dreg.numel() == rows * 4 and dreg.dtype == logits.dtype and reg_t.numel() == rows * 4
+            and state.numel() == rows and state.dtype == torch.int8):
+        raise ValueError("box_dist_fwd_bwd: dreg (rows, 4) of the logits' dtype, reg_t (rows, 4) and state (rows,) int8 "
+                         "expected")
+    if not 2 <= K <= 32 or _dist_dt(logits) == 2 or rows == 0:
+        raise NotServed("box_dist_fwd_bwd")
+    npos = _npos(state, npos)
+    ld = 0
+    if grad_out is not None:
+        ld = grad_out.shape[-1]
+        if not (grad_out.is_contiguous() and grad_out.dtype == logits.dtype and group > 0 and rows % group == 0
+                and ld >= group * 4 * K and grad_out.numel() == rows // group * ld):
+            raise ValueError("box_dist_fwd_bwd: grad_out does not match the padded layout")
+        grad = grad_out
+    else:
+        grad = torch.empty_like(logits)
+    part = torch.empty(LOSS_GRID, dtype=torch.float32, device=logits.device)
+    out = torch.empty(1, dtype=torch.float32, device=logits.device)
+    rc = lib().mxr_box_dist_fwd_bwd(_p(logits), _p(dreg.contiguous()), _p(reg_t.float().contiguous()),
+                                    _p(state.contiguous()), _p(npos), _p(grad), _p(part), _p(out), rows, K, float(R),
+                                    float(weight), _dist_dt(logits), int(group) if ld else 0, ld, _s())
+    if rc == -1:
+        raise NotServed("box_dist_fwd_bwd")
+    _chk(rc, "box_dist_fwd_bwd")
+    return out.reshape(()), grad
+
+
+class BoxIntegralFn(torch.autograd.Function):
+    """``box_integral`` on the kernels (every row); the backward is ``box_dist_fwd_bwd`` with every row positive and a
+    DFL weight of 0, which leaves the integral's ``g p_i (v_i - y)``."""
+
+    @staticmethod
+    def forward(ctx, logits, K, R):
+        out = box_integral_fwd(logits, K, R)
+        ctx.save_for_backward(logits)
+        ctx.cfg = (int(K), float(R))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (logits,) = ctx.saved_tensors
+        K, R = ctx.cfg
+        rows = logits.numel() // (4 * K)
+        if rows == 0:
+            return torch.zeros_like(logits), None, None
+        every = torch.ones(rows, dtype=torch.int8, device=logits.device)
+        target = torch.zeros(rows, 4, dtype=torch.float32, device=logits.device)
+        _, dl = box_dist_fwd_bwd(logits, g.to(logits.dtype).contiguous(), target, every,
+                                 torch.ones(1, dtype=torch.int32, device=logits.device), K, R, weight=0.0)
+        return dl, None, None
+
+
+class DistributionFocalLossFn(torch.autograd.Function):
+    """The DFL term alone: ``box_dist_fwd_bwd`` with a zero delta gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, reg_t, state, K, R, weight, npos=None):
+        dreg = torch.zeros(logits.shape[:-1] + (4,), dtype=logits.dtype, device=logits.device)
+        loss, grad = box_dist_fwd_bwd(logits, dreg, reg_t, state, npos, K, R, weight)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g.to(grad.dtype), None, None, None, None, None, None
 
 
 class QualityLossFn(torch.autograd.Function):

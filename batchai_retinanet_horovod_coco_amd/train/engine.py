@@ -55,8 +55,22 @@ class Trainer:
                  device: Optional[torch.device] = None, overlap: bool = True, target_backend: str = "auto",
                  optimizer: str = "adam", momentum: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0,
                  ema_decay: float = 0.0, regression_loss: str = "smooth_l1", regression_weight: float = 1.0,
-                 assigner: str = "iou", atss_topk: int = anchor_ops.ATSS_TOPK, classification_loss: str = "focal"):
+                 assigner: str = "iou", atss_topk: int = anchor_ops.ATSS_TOPK, classification_loss: str = "focal",
+                 dfl_weight: float = losses.DFL_WEIGHT):
         from ..parallel.collectives import Compression
+        # a distribution box head (RetinaNet(regression_bins=K)): the box loss on its integral deltas plus DFL
+        self.regression_bins = int(getattr(model, "regression_bins", 0) or 0)
+        self.regression_range = float(getattr(model, "regression_range", 8.0))
+        if not self.regression_bins and dfl_weight != losses.DFL_WEIGHT:
+            raise ValueError("dfl_weight goes with a distribution box head (regression_bins); this model has none")
+        if not float(dfl_weight) >= 0:
+            raise ValueError("dfl_weight must be >= 0, got {}".format(dfl_weight))
+        self.dfl_weight = float(dfl_weight)
+        if self.regression_bins:
+            from ..ops import fp8 as _fp8
+            if _fp8.enabled():
+                raise ValueError("regression_bins={} does not go with fp8: the regression final's {} outputs would run "
+                                 "in fp8".format(self.regression_bins, 4 * self.regression_bins * model.num_anchors))
         if classification_loss != "focal" and classification_loss not in losses.CLS_KINDS:
             raise ValueError("classification_loss must be 'focal' or one of {}, got {!r}".format(
                 losses.CLS_KINDS, classification_loss))
@@ -109,6 +123,8 @@ class Trainer:
             # likewise the target assignment
             self.base_optimizer.assigner = assigner
             self.base_optimizer.atss_topk = self.atss_topk
+        if self.dfl_weight != losses.DFL_WEIGHT:
+            self.base_optimizer.dfl_weight = self.dfl_weight
         self.anchors = anchor_ops.AnchorCache()
         self.num_classes = model.num_classes
         self.target_backend = target_backend
@@ -166,12 +182,17 @@ class Trainer:
             state, label, reg_t, npos = self.compute_targets(images, gt, gt_count, image_hw)
         x = images.to(self.compute_dtype)
         req = self._focal_request(state, label, npos)
+        if self.regression_bins and self._fused_losses():
+            # the distribution head's integral runs on positive rows only (RetinaNet._with_integral)
+            self.model.integral_request = state
         with _range("forward"):
             try:
                 out = self.model(x)
             finally:
                 if req is not None:
                     self.model.focal_request = None
+                if self.regression_bins:
+                    self.model.integral_request = None
         with _range("backward"):
             return self._losses_backward(out, reg_t, state, label, npos, self._loss_anchors(images))
 
@@ -196,6 +217,42 @@ class Trainer:
             return losses.smooth_l1_loss(reg, reg_t, state, backend="torch")
         return losses.iou_loss(reg, reg_t, state, anchors, self.regression_loss, self.regression_weight,
                                backend="torch")
+
+    def _regression_terms_torch(self, out, reg_t, state, anchors):
+        """The logged regression loss as torch expressions: the box loss and, with a distribution head, + DFL."""
+        loss = self._regression_torch(out["regression"], reg_t, state, anchors)
+        if self.regression_bins:
+            loss = loss + losses.distribution_focal_loss(out["regression_logits"], reg_t, state, self.regression_bins,
+                                                         self.regression_range, self.dfl_weight, backend="torch")
+        return loss
+
+    def _dist_losses_fused(self, out, reg_t, state, npos, anchors, A, rsink):
+        """The fused losses of a distribution head: the box loss kernel on the integral deltas (plain gradient layout),
+        then box_dist.hip: DFL and d(box loss + DFL)/d(logits), into the regression final's zero-padded rows where it
+        has them.  Returns (the tensor to backpropagate from, regression loss, its gradient)."""
+        from ..ops import native
+        from ..ops import fp8 as _fp8
+        if _fp8.enabled():      # switched on after the constructor's check
+            raise RuntimeError("regression_bins={} does not go with fp8".format(self.regression_bins))
+        K, R = self.regression_bins, self.regression_range
+        logits, reg = out["regression_logits"], out["regression"]
+        if reg.requires_grad:
+            # the model ran the differentiable torch integral (a form box_dist.hip does not serve)
+            loss = self._regression_terms_torch(out, reg_t, state, anchors)
+            return loss, loss, None
+        box_loss, dreg = self._regression_fwd_bwd(reg, reg_t, state, npos, anchors)
+        W = 4 * K * A
+        if rsink is not None and _PAD_FOCAL and logits.dtype == torch.bfloat16 and logits.shape[1] % A == 0 and W % 64:
+            key = (logits.shape[0], logits.shape[1] // A, (W + 63) // 64 * 64, logits.device)
+            buf = self._reg_pad_buf.get(key, lambda: torch.zeros(key[:3], dtype=logits.dtype, device=logits.device))
+            dfl, dpad = native.box_dist_fwd_bwd(logits.detach(), dreg, reg_t, state, npos, K, R, self.dfl_weight,
+                                                grad_out=buf, group=A)
+            rsink["dy"] = dpad
+            dlog = torch.zeros((), dtype=logits.dtype, device=logits.device).expand(logits.shape)
+        else:
+            # (W % 64 == 0: the plain layout is the final layer's own)
+            dfl, dlog = native.box_dist_fwd_bwd(logits.detach(), dreg, reg_t, state, npos, K, R, self.dfl_weight)
+        return logits, box_loss + dfl, dlog
 
     def _check_quality_rows(self, cls, reg, anchors):
         """An IoU-aware classification loss reads row r of the regression output for row r of the logits."""
@@ -255,7 +312,9 @@ class Trainer:
             reg = out["regression"]
             A = self.model.num_anchors if hasattr(self.model, "num_anchors") else 9
             rsink = getattr(self.model, "reg_pad_sink", None)
-            if rsink is not None and _PAD_FOCAL and reg.dtype == torch.bfloat16 and reg.shape[1] % A == 0 and \
+            if self.regression_bins:
+                reg, reg_loss, dreg = self._dist_losses_fused(out, reg_t, state, npos, anchors, A, rsink)
+            elif rsink is not None and _PAD_FOCAL and reg.dtype == torch.bfloat16 and reg.shape[1] % A == 0 and \
                     (4 * A) % 64:
                 # the loss kernel writes d(loss)/d(regression) into the final layer's 64-padded rows (36 -> 64);
                 # the layer's data / weight / bias gradients then read them as is (no pad, cast or slice)
@@ -290,7 +349,7 @@ class Trainer:
                 cls_loss, dcls = self._classification_fwd_bwd(out, reg_t, state, label, npos, anchors)
             torch.autograd.backward([reg, cls], [dreg, dcls])
         else:
-            reg_loss = self._regression_torch(out["regression"], reg_t, state, anchors)
+            reg_loss = self._regression_terms_torch(out, reg_t, state, anchors)
             cls_loss = self._classification_torch(out, reg_t, state, label, anchors)
             (reg_loss + cls_loss).backward()
         return reg_loss.detach(), cls_loss.detach()
@@ -301,7 +360,7 @@ class Trainer:
             state, label, reg_t, npos = self.compute_targets(images, gt, gt_count, image_hw)
             out = self.model(images.to(self.compute_dtype))
             anchors = self._loss_anchors(images)
-            reg_loss = self._regression_torch(out["regression"], reg_t, state, anchors)
+            reg_loss = self._regression_terms_torch(out, reg_t, state, anchors)
             cls_loss = self._classification_torch(out, reg_t, state, label, anchors)
         return reg_loss, cls_loss
 
