@@ -539,3 +539,208 @@ def atss_targets_torch(anchors: torch.Tensor, levels, gt: torch.Tensor, gt_count
         sel = torch.where(valid[..., None, None], sel, torch.full_like(sel, -1))
         return state, label, reg, thr, sel
     return state, label, reg
+
+
+# ----------------------------------------------------------------------------------------
+# TAL (Feng et al., "TOOD", ICCV 2021, section 3.2): positives from the predictions
+# ----------------------------------------------------------------------------------------
+TAL_TOPK = 13
+TAL_MAX_TOPK = ATSS_MAX_TOPK
+TAL_BETA = 6            # t = s^1 u^6; no flags, as with QFL's beta
+TAL_EPS = 1e-7
+
+
+def _tal_centres(lv: np.ndarray, A0: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Per anchor the grid centre of its location, from the level table: ``((ix + .5) * stride, (iy + .5) * stride)``."""
+    cx, cy = [], []
+    for first, h, w, stride in lv.tolist():
+        loc = np.arange(h * w)
+        cx.append(np.repeat((loc % w + 0.5) * stride, A0))
+        cy.append(np.repeat((loc // w + 0.5) * stride, A0))
+    return np.concatenate(cx), np.concatenate(cy)
+
+
+def tal_assign(anchors: np.ndarray, levels, boxes: np.ndarray, cls_logits: np.ndarray, reg: np.ndarray,
+               topk: int = TAL_TOPK) -> dict:
+    """Task-aligned assignment for one image in float64, brute force: the specification of the torch form (and of
+    device kernels, which do not exist yet).  ``boxes`` (n, 5) ``[x1, y1, x2, y2, label]``, ``cls_logits`` (A, C),
+    ``reg`` (A, 4) deltas.
+
+    Anchor i's predicted box is ``bbox_transform_inv`` (mean 0, std 0.2) of its deltas with the corners ordered;
+    ``u_ij = inter / (area_p + area_g - inter + 1e-7)``; ``t_ij = sigmoid(x[i, label_j]) * u_ij^6`` (the power by
+    multiplications).  i is a candidate of j when the grid centre of its location lies inside the box (ATSS's test)
+    and ``u_ij > 0``; a box selects its ``min(topk, n_j)`` candidates of largest t, ordered by (t descending, anchor
+    index ascending); an anchor selected by several boxes takes the box of largest u, the lowest index in a tie.  Per
+    box, over the anchors it finally holds, ``tmax`` and ``umax``; a held anchor's quality is
+    ``t / (tmax + 1e-7) * umax``.
+
+    Returns ``arg`` (A,) the box of every anchor or -1, ``quality`` (A,), ``u`` / ``t`` / ``candidate`` / ``selected``
+    (n, A), ``cutoff`` (n, 2) the t of the last selected and of the first not selected candidate (nan where there is
+    none), ``count`` (n,) the candidates per box, ``tmax`` / ``umax`` (n,)."""
+    topk = _check_topk(topk)
+    anchors = np.asarray(anchors, dtype=np.float64)
+    A = anchors.shape[0]
+    lv, A0 = _check_levels(levels, A)
+    boxes = np.asarray(boxes, dtype=np.float64).reshape(-1, 5)
+    x = np.asarray(cls_logits, dtype=np.float64)
+    d = np.asarray(reg, dtype=np.float64)
+    n = boxes.shape[0]
+    aw, ah = anchors[:, 2] - anchors[:, 0], anchors[:, 3] - anchors[:, 1]
+    qx1, qy1 = anchors[:, 0] + d[:, 0] * BOX_STD * aw, anchors[:, 1] + d[:, 1] * BOX_STD * ah
+    qx2, qy2 = anchors[:, 2] + d[:, 2] * BOX_STD * aw, anchors[:, 3] + d[:, 3] * BOX_STD * ah
+    px1, px2, py1, py2 = np.minimum(qx1, qx2), np.maximum(qx1, qx2), np.minimum(qy1, qy2), np.maximum(qy1, qy2)
+    ccx, ccy = _tal_centres(lv, A0)
+    out = {"arg": np.full(A, -1, dtype=np.int64), "quality": np.zeros(A), "u": np.zeros((n, A)), "t": np.zeros((n, A)),
+           "candidate": np.zeros((n, A), dtype=bool), "selected": np.zeros((n, A), dtype=bool),
+           "cutoff": np.full((n, 2), np.nan), "count": np.zeros(n, dtype=np.int64), "tmax": np.zeros(n),
+           "umax": np.zeros(n)}
+    best = np.zeros(A)
+    idx = np.arange(A)
+    for j in range(n):
+        x1, y1, x2, y2 = boxes[j, :4]
+        iw = np.clip(np.minimum(px2, x2) - np.maximum(px1, x1), 0, None)
+        ih = np.clip(np.minimum(py2, y2) - np.maximum(py1, y1), 0, None)
+        inter = iw * ih
+        u = inter / ((px2 - px1) * (py2 - py1) + (x2 - x1) * (y2 - y1) - inter + TAL_EPS)
+        with np.errstate(over="ignore"):                    # exp overflows to inf for a very negative logit: s = 0
+            s = 1.0 / (1.0 + np.exp(-x[:, int(boxes[j, 4])]))
+        u2 = u * u
+        t = s * (u2 * u2 * u2)
+        inside = np.minimum(np.minimum(ccx - x1, ccy - y1), np.minimum(x2 - ccx, y2 - ccy)) > ATSS_INSIDE_EPS
+        cand = inside & (u > 0)
+        c = idx[cand]
+        order = c[np.lexsort((c, -t[c]))]                   # (t descending, index ascending)
+        take = order[:topk]
+        out["u"][j], out["t"][j], out["candidate"][j], out["count"][j] = u, t, cand, c.size
+        out["selected"][j, take] = True
+        if take.size:
+            out["cutoff"][j, 0] = t[take[-1]]
+        if order.size > topk:
+            out["cutoff"][j, 1] = t[order[topk]]
+        win = take[u[take] > best[take]]                    # strict: the lower box index keeps a tie
+        best[win] = u[win]
+        out["arg"][win] = j
+    for j in range(n):
+        held = out["arg"] == j
+        if held.any():
+            out["tmax"][j], out["umax"][j] = out["t"][j, held].max(), out["u"][j, held].max()
+            out["quality"][held] = out["t"][j, held] / (out["tmax"][j] + TAL_EPS) * out["umax"][j]
+    return out
+
+
+def tal_targets_bbox(image_shape, annotations: np.ndarray, cls_logits: np.ndarray, reg: np.ndarray, mask_shape=None,
+                     topk: int = TAL_TOPK, shapes_callback=None, anchors: Optional[np.ndarray] = None):
+    """Task-aligned targets for one image, the float64 oracle: ``(labels (A, C) with -1 rows for ignore, regression
+    (A, 4), state (A,), quality (A,))``.  Positives get state 1, the box's label and the usual regression target;
+    everything else state 0, label 0 and a zero regression target -- there is no ignore band -- except that anchors
+    centred outside the image are ignored last, positives included (their quality is 0 like every non-positive row's)."""
+    if anchors is None:
+        anchors = anchors_for_shape(image_shape, shapes_callback=shapes_callback)
+    anchors = np.asarray(anchors, dtype=np.float64)
+    A = anchors.shape[0]
+    num_classes = np.asarray(cls_logits).shape[-1]
+    annotations = np.asarray(annotations, dtype=np.float64).reshape(-1, 5)
+    r = tal_assign(anchors, level_table(image_shape, shapes_callback), annotations, cls_logits, reg, topk)
+    pos = r["arg"] >= 0
+    labels = np.zeros((A, num_classes))
+    state = np.zeros((A,))
+    regression = np.zeros((A, 4))
+    if pos.any():
+        matched = annotations[r["arg"][pos]]
+        labels[np.nonzero(pos)[0], matched[:, 4].astype(int)] = 1
+        state[pos] = 1
+        regression[pos] = bbox_transform(anchors[pos], matched[:, :4])
+    mh, mw = (image_shape if mask_shape is None else mask_shape)[:2]
+    cx = (anchors[:, 0] + anchors[:, 2]) / 2
+    cy = (anchors[:, 1] + anchors[:, 3]) / 2
+    outside = (cx >= mw) | (cy >= mh)
+    labels[outside, :] = -1
+    state[outside] = -1
+    return labels, regression, state, np.where(state == 1, r["quality"], 0.0)
+
+
+def tal_targets_torch(anchors: torch.Tensor, levels, gt: torch.Tensor, gt_count: torch.Tensor, mask_hw: torch.Tensor,
+                      cls_logits: torch.Tensor, reg: torch.Tensor, topk: int = TAL_TOPK,
+                      centers: Optional[torch.Tensor] = None):
+    """Batched fp32 task-aligned targets: the arithmetic of
+    ``tal_assign`` in fp32 torch ops, one image at a time ((G, A) intermediates).  ``cls_logits`` (B, A, C) and ``reg``
+    (B, A, 4) are the model's detached outputs in any float dtype.  Returns ``(state (B, A) int8, label (B, A) int32,
+    regression (B, A, 4) f32, quality (B, A) f32)``; nothing depends on the data in shape or control flow."""
+    topk = _check_topk(topk)
+    B, G = gt.shape[0], gt.shape[1]
+    A = anchors.shape[0]
+    dev = anchors.device
+    lv, A0 = _check_levels(levels, A)
+    f32 = torch.float32
+    C = cls_logits.shape[-1]
+    if cls_logits.shape[:2] != (B, A) or reg.shape != (B, A, 4):
+        raise ValueError("tal_targets_torch: logits (B, A, C) and deltas (B, A, 4) for {} images of {} anchors expected, "
+                         "got {} and {}".format(B, A, tuple(cls_logits.shape), tuple(reg.shape)))
+    gt = gt.to(f32)
+    cnt = gt_count.to(dev).to(torch.int64)
+    cc = _tal_centres(lv, A0)
+    ccx, ccy = torch.from_numpy(cc[0]).to(dev, f32), torch.from_numpy(cc[1]).to(dev, f32)
+    a1, b1, a2, b2 = anchors.to(f32).unbind(-1)
+    aw, ah = a2 - a1, b2 - b1
+    zero = torch.zeros((), dtype=f32, device=dev)
+    k = min(topk, A)
+    states, labels, regs, quals = [], [], [], []
+    for b in range(B if G else 0):
+        d = reg[b].detach().to(f32)
+        qx1, qy1 = a1 + (d[:, 0] * BOX_STD) * aw, b1 + (d[:, 1] * BOX_STD) * ah
+        qx2, qy2 = a2 + (d[:, 2] * BOX_STD) * aw, b2 + (d[:, 3] * BOX_STD) * ah
+        px1, px2 = torch.minimum(qx1, qx2), torch.maximum(qx1, qx2)
+        py1, py2 = torch.minimum(qy1, qy2), torch.maximum(qy1, qy2)
+        valid = (torch.arange(G, device=dev) < cnt[b])[:, None]                      # (G, 1)
+        # rows past the count may hold anything: they are replaced before any arithmetic
+        box = torch.where(valid, gt[b, :, :4], zero)
+        lab = torch.where(valid[:, 0], gt[b, :, 4], zero).to(torch.int64).clamp(0, C - 1)
+        x1, y1, x2, y2 = [box[:, i, None] for i in range(4)]
+        iw = (torch.minimum(px2, x2) - torch.maximum(px1, x1)).clamp_min(0)
+        ih = (torch.minimum(py2, y2) - torch.maximum(py1, y1)).clamp_min(0)
+        inter = iw * ih
+        u = inter / ((((px2 - px1) * (py2 - py1))[None] + (x2 - x1) * (y2 - y1) - inter) + TAL_EPS)   # (G, A)
+        xs = cls_logits[b].detach().to(f32)[:, lab].t()                                                 # (G, A)
+        s = 1.0 / (1.0 + torch.exp(-xs))
+        u2 = u * u
+        t = s * (u2 * u2 * u2)
+        inside = torch.minimum(torch.minimum(ccx - x1, ccy - y1), torch.minimum(x2 - ccx, y2 - ccy)) > ATSS_INSIDE_EPS
+        cand = inside & (u > 0) & valid
+        # (t descending, index ascending): a stable ascending sort of -t, the non-candidates last
+        order = torch.sort(torch.where(cand, -t, torch.ones_like(t)), dim=1, stable=True)[1][:, :k]
+        sel = torch.zeros_like(cand).scatter_(1, order, True) & cand
+        score = torch.where(sel, u, -torch.ones_like(u))
+        best = score.max(dim=0)[0]                                                                      # (A,)
+        is_pos = best > 0
+        gidx = torch.arange(G, device=dev)[:, None].expand(G, A)
+        arg = torch.where(sel & (score == best[None]), gidx, torch.full_like(gidx, G)).min(dim=0)[0]
+        argc = arg.clamp(max=G - 1)
+        held = (gidx == arg[None]) & is_pos[None]
+        tmax = torch.where(held, t, zero).max(dim=1)[0]
+        umax = torch.where(held, u, zero).max(dim=1)[0]
+        ta = t.gather(0, argc[None])[0]
+        q = torch.where(is_pos, ta / (tmax[argc] + TAL_EPS) * umax[argc], zero)
+        matched = gt[b][argc]
+        r = torch.stack([(matched[:, 0] - a1) / aw, (matched[:, 1] - b1) / ah,
+                         (matched[:, 2] - a2) / aw, (matched[:, 3] - b2) / ah], -1)
+        r = (r - BOX_MEAN) / BOX_STD
+        regs.append(torch.where(is_pos[:, None], r, zero))
+        labels.append(torch.where(is_pos, matched[:, 4].to(torch.int32), torch.zeros((), dtype=torch.int32, device=dev)))
+        states.append(is_pos.to(torch.int8))
+        quals.append(q)
+    if G:
+        state, label, regression, quality = (torch.stack(states), torch.stack(labels), torch.stack(regs),
+                                             torch.stack(quals))
+    else:
+        state = torch.zeros((B, A), dtype=torch.int8, device=dev)
+        label = torch.zeros((B, A), dtype=torch.int32, device=dev)
+        regression = torch.zeros((B, A, 4), dtype=f32, device=dev)
+        quality = torch.zeros((B, A), dtype=f32, device=dev)
+    if centers is None:
+        centers = torch.from_numpy(centers_round_down(anchors.double().cpu().numpy())).to(dev)
+    mh = mask_hw[:, 0].to(dev).to(f32)[:, None]
+    mw = mask_hw[:, 1].to(dev).to(f32)[:, None]
+    outside = (centers[None, :, 0] >= mw) | (centers[None, :, 1] >= mh)
+    state = torch.where(outside, torch.full_like(state, -1), state)
+    quality = torch.where(state == 1, quality, zero)
+    return state, label, regression, quality

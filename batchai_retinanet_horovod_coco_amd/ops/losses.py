@@ -189,10 +189,14 @@ def _softplus(x):
     return x.clamp_min(0) + torch.log1p(torch.exp(-x.abs()))
 
 
-def _quality_torch(logits, reg, reg_t, state, label, anchors, kind):
+def _quality_torch(logits, reg, reg_t, state, label, anchors, kind, quality=None):
     x = logits if logits.dtype == torch.float64 else logits.float()
     B, A, C = x.shape
-    q = quality_targets(anchors, reg.to(x.dtype), reg_t, state)
+    if quality is None:
+        q = quality_targets(anchors, reg.to(x.dtype), reg_t, state)
+    else:
+        q = torch.where(state == 1, quality.detach().to(x.dtype).reshape(B, A), torch.zeros((), dtype=x.dtype,
+                                                                                             device=x.device))
     pos = (state == 1)
     keep = (state != -1)[..., None].to(x.dtype)
     t = torch.zeros_like(x)
@@ -208,21 +212,28 @@ def _quality_torch(logits, reg, reg_t, state, label, anchors, kind):
     return loss / torch.clamp(pos.sum().to(x.dtype), min=1.0)
 
 
-def quality_loss(logits: torch.Tensor, reg: torch.Tensor, reg_t: torch.Tensor, state: torch.Tensor,
-                 label: torch.Tensor, anchors: torch.Tensor, kind: str, backend: str = "auto") -> torch.Tensor:
+def quality_loss(logits: torch.Tensor, reg: Optional[torch.Tensor], reg_t: Optional[torch.Tensor], state: torch.Tensor,
+                 label: torch.Tensor, anchors: Optional[torch.Tensor], kind: str, backend: str = "auto",
+                 quality: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Quality Focal Loss (``kind="qfl"``: Li et al. 2020, beta = 2) or Varifocal Loss (``"vfl"``: Zhang et al. 2021,
     alpha = 0.75, gamma = 2) on logits (B, A, C): the label class of a positive anchor is trained towards
     ``quality_targets`` (the IoU of its predicted box, no gradient into ``reg``), every other class towards 0.  Summed
     over the anchors whose state is not -1 and divided by max(1, #positives), without Keras' probability clip.  The
-    torch expression computes in fp32, or in float64 when the logits are float64 (the kernel's oracle)."""
+    torch expression computes in fp32, or in float64 when the logits are float64 (the kernel's oracle).  ``quality``
+    (B, A): the soft target itself (a task-aligned assignment's, ``ops.anchors.tal_targets_bbox``) in place of the IoU;
+    ``reg``, ``reg_t`` and ``anchors`` are then not read and may be None.  Only the torch expression takes it: no kernel
+    reads a given target, and asking the HIP backend for one is an error."""
     from . import native
     if kind not in CLS_KINDS:
         raise ValueError("kind must be one of {}, got {!r}".format(CLS_KINDS, kind))
     if backend == "auto":
         backend = "hip" if (logits.is_cuda and native.available()) else "torch"
+    if quality is not None and backend == "hip":
+        raise RuntimeError("quality_loss: quality_loss.hip has no HIP kernel that reads a given target; "
+                           "backend=\"torch\" is the expression")
     if backend == "hip":
         return native.QualityLossFn.apply(logits, reg, reg_t, state, label, anchors, kind)
-    return _quality_torch(logits, reg, reg_t, state, label, anchors, kind)
+    return _quality_torch(logits, reg, reg_t, state, label, anchors, kind, quality)
 
 
 DFL_WEIGHT = 0.25
