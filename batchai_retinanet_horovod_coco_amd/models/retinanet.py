@@ -111,11 +111,13 @@ class Submodel(nn.Module):
         w, b = self.final.effective(x[0].dtype)
         return conv_ops.pyramid_conv(x, w, b, relu=False)
 
-    def forward_packed(self, x: torch.Tensor, shapes, pad_sink=None, join=None) -> torch.Tensor:
+    def forward_packed(self, x: torch.Tensor, shapes, pad_sink=None, join=None, chain=None) -> torch.Tensor:
         """All 5 levels as ONE ragged GEMM per layer on packed [B, P, C] features.
 
         ``pad_sink``: dict through which the loss may hand the final layer its gradient already in
-        zero-padded rows (see :attr:`RetinaNet.cls_pad_sink`)."""
+        zero-padded rows (see :attr:`RetinaNet.cls_pad_sink`); ``chain``: the ``ops.row_activity.GradChain`` of a
+        tower whose loss gradient is sparse (the regression submodel; bf16 without a norm -- a norm's backward
+        makes the gradient dense)."""
         from ..ops import native_conv
         from ..ops import fp8
         if self.norms is not None:
@@ -137,9 +139,10 @@ class Submodel(nn.Module):
             nxt = self.tower[i + 1] if i + 1 < len(self.tower) else self.final
             x = native_conv.pyramid_conv_layer(x, shapes, c, True, mask_input_grad=i > 0, grad_premasked=True,
                                                join=join if i == 0 else None,
-                                               out_f8=fp8.eligible(nxt.cin, nxt.cout))
+                                               out_f8=fp8.eligible(nxt.cin, nxt.cout),
+                                               act=None if chain is None else (chain, len(self.tower) - i))
         return native_conv.pyramid_conv_layer(x, shapes, self.final, False, mask_input_grad=True,
-                                              pad_sink=pad_sink)
+                                              pad_sink=pad_sink, act=None if chain is None else (chain, 0))
 
     def convs(self) -> List[Conv2D]:
         return list(self.tower) + [self.final]
@@ -214,7 +217,14 @@ class RetinaNet(nn.Module):
             # the compute stream: a second stream for the regression tower measured 461.7 vs 468.8-473.2
             # img/s with hx32, profiles/r3_ab_knobs.txt, and was removed.)
             self.reg_pad_sink = {} if torch.is_grad_enabled() else None
-            reg = self.regression_submodel.forward_packed(packed, shapes, self.reg_pad_sink, join=join)
+            # the regression loss has a gradient on positive anchors only: its tower's backward skips the tiles
+            # that multiply zeros (ops.row_activity; MXR_SPARSE_REG_GRAD=0: dense)
+            from ..ops import fp8, row_activity
+            chain = None
+            if (torch.is_grad_enabled() and row_activity.enabled() and packed.dtype == torch.bfloat16
+                    and self.head_norm is None and not fp8.enabled()):
+                chain = row_activity.GradChain(len(self.regression_submodel.tower))
+            reg = self.regression_submodel.forward_packed(packed, shapes, self.reg_pad_sink, join=join, chain=chain)
             # The classification final layer's data gradient runs on 64-padded rows (720 -> 768): a
             # loss kernel may write its gradient there directly (Trainer._losses_backward) instead of
             # autograd handing over (B, A, 80) rows that then get padded -- one 0.5 GB copy per step.

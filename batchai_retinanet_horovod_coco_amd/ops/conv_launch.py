@@ -17,6 +17,7 @@ import torch.nn.functional as F
 
 from . import halo as _hx
 from . import native as _n
+from . import row_activity as _ra
 from .native import ConvGeom, _chk, _p, _s, lib, zero_page, c_int, c_ll, c_vp
 from .side_stream import SIDE
 
@@ -273,9 +274,12 @@ def launch_halo(x, w, bias, res, y, g: ConvGeom, relu: bool, accumulate: bool = 
          "conv3x3_halo")
 
 def launch_hx32(x, w, bias, res, y, g: ConvGeom, relu: bool, accumulate: bool = False, variant: int = 0,
-                mask: Optional[torch.Tensor] = None) -> None:
+                mask: Optional[torch.Tensor] = None, active=None) -> None:
     """3x3 / stride-1 / pad-1 conv on the 32x32x16 MFMA (variants 10-15: the 16x16x32 MFMA) with plane-split LDS
-    images (csrc/kernels/conv_hx32.hip; same tile table as :func:`launch_halo`)."""
+    images (csrc/kernels/conv_hx32.hip; same tile table as :func:`launch_halo`).
+    ``active`` (an ``ops.row_activity.Activity``; default: the one of the enclosing ``row_activity.using`` block): a
+    data gradient whose input ``x`` is zero outside that support -- only the active halo tiles are computed, the
+    others get zeros (nothing when accumulating); bit-identical to the dense launch."""
     if not hx32_covers(g):
         raise RuntimeError("conv3x3_hx32: geometry not covered")
     if not (x.is_contiguous() and w.is_contiguous() and y.is_contiguous() and x.shape[-1] == g.cin
@@ -286,6 +290,12 @@ def launch_hx32(x, w, bias, res, y, g: ConvGeom, relu: bool, accumulate: bool = 
         variant = {2: 0, 3: 1, 13: 10, 14: 12}.get(variant, variant)
     tiles, nt = _hx.device_tiles(_hx.geom_batch(g), _hx.geom_shapes(g), x.device)
     wp = hx32_packed(w, g.cout, g.cin)
+    act = active if active is not None else _ra.current()
+    if act is not None and act.M == int(g.M) and act.ntiles == nt and bias is None and res is None and not relu:
+        _ra.LAUNCHES["dgrad"] += 1
+        return _chk(lib().mxr_conv3x3_hx32_act(_p(x), _p(wp), None, None, _p(mask), _p(y), _p(zero_page(x.device)),
+                                               ctypes.byref(g), _p(tiles), nt, 0, int(accumulate), int(variant),
+                                               _p(act.order), _p(act.count), _s()), "conv3x3_hx32_act")
     _chk(lib().mxr_conv3x3_hx32(_p(x), _p(wp), _p(bias), _p(res), _p(mask), _p(y), _p(zero_page(x.device)),
                                 ctypes.byref(g), _p(tiles), nt, int(relu), int(accumulate), int(variant), _s()),
          "conv3x3_hx32")

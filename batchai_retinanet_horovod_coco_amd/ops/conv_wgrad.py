@@ -14,6 +14,7 @@ import torch.nn.functional as F
 from . import native as _n
 from .native import ConvGeom, _chk, _p, _s, lib, zero_page, c_int, c_ll, c_vp
 from .side_stream import SIDE
+from . import row_activity as _ra
 from .conv_launch import (_bind, _miopen_wgrad, _only, geom_single)
 
 
@@ -86,11 +87,14 @@ def _splits_pipe(g: ConvGeom, tk: int, tc: int, occ: int = 1) -> int:
 
 def conv_wgrad(x, dy, g: ConvGeom, scale: Optional[torch.Tensor], out: Optional[torch.Tensor] = None,
                accumulate: bool = False, variant: Optional[int] = None, bias_out: Optional[torch.Tensor] = None,
-               bias_accumulate: bool = False, splits: Optional[int] = None) -> torch.Tensor:
+               bias_accumulate: bool = False, splits: Optional[int] = None, rowmask=None) -> torch.Tensor:
     """fp32 dW (OHWI) = scale[co] * sum_m dY (x) im2col(X); dY may have cout % 8 != 0 (padded).
     ``splits``: the pixel-split count of the split-K forms (default: the per-kernel heuristic).
     ``bias_out`` (phase-pipelined variants, see :data:`_WGRAD_P8`, cout % 4 == 0): the unscaled bias
-    gradient sum_m dY[m, :cout] is computed by the same kernel from the dY tiles it stages anyway."""
+    gradient sum_m dY[m, :cout] is computed by the same kernel from the dY tiles it stages anyway.
+    ``rowmask`` (an ``ops.row_activity.Activity``; default: the one of the enclosing ``row_activity.using`` block):
+    the rows of ``dy`` outside it are all zero -- the phase-pipelined variants skip the 64-row K-tiles without a set
+    row (bit-identical to the dense walk); the other variants run dense."""
     cout = g.cout
     K = g.kh * g.kw * g.cin
     ldy = dy.shape[-1]
@@ -120,6 +124,14 @@ def conv_wgrad(x, dy, g: ConvGeom, scale: Optional[torch.Tensor], out: Optional[
         splits = splits or _splits_pipe(g, 256, 256)
         nb = 0 if bias_out is None else splits * cout
         part = torch.empty(splits * cout * K + nb, dtype=torch.float32, device=dy.device)
+        act = rowmask if rowmask is not None else _ra.current()
+        if act is not None and act.M == int(g.M) and dy.numel() == int(g.M) * ldy:
+            _ra.LAUNCHES["wgrad"] += 1
+            _chk(lib().mxr_conv_wgrad_p8_bias_act(_p(x), _p(dy), ldy, _p(part), splits, _p(out), _p(sc),
+                                                  int(accumulate), _p(zero_page(dy.device)), ctypes.byref(g),
+                                                  _WGRAD_P8[variant], _p(bias_out), int(bias_accumulate),
+                                                  _p(act.words), _s()), "conv_wgrad_p8_act")
+            return out
         _chk(lib().mxr_conv_wgrad_p8_bias(_p(x), _p(dy), ldy, _p(part), splits, _p(out), _p(sc), int(accumulate),
                                           _p(zero_page(dy.device)), ctypes.byref(g), _WGRAD_P8[variant],
                                           _p(bias_out), int(bias_accumulate), _s()),

@@ -166,6 +166,67 @@ def emulate(x: np.ndarray, w: np.ndarray, tab: np.ndarray) -> np.ndarray:
     return y
 
 
+# ---- row activity (csrc/kernels/row_activity.hip): numpy references of the bit layout, the dilation and the
+# tile-activity rule
+
+def pack_row_bits(rows: np.ndarray) -> np.ndarray:
+    """bool [P] -> uint64 words: bit ``m % 64`` of word ``m // 64`` is row ``m`` (word t = the 64-row K-tile t of the
+    phase-pipelined weight gradient); the bits past P are clear."""
+    P = int(rows.shape[0])
+    pad = np.zeros((P + 63) // 64 * 64, dtype=np.uint64)
+    pad[:P] = rows.astype(np.uint64)
+    return (pad.reshape(-1, 64) << np.arange(64, dtype=np.uint64)).sum(axis=1, dtype=np.uint64)
+
+
+def unpack_row_bits(words: np.ndarray, P: int) -> np.ndarray:
+    w = np.asarray(words).view(np.uint64).reshape(-1, 1)
+    return ((w >> np.arange(64, dtype=np.uint64)) & np.uint64(1)).astype(bool).reshape(-1)[:P]
+
+
+def dilate_rows(rows: np.ndarray, N: int, shapes: Sequence[Tuple[int, int]]) -> np.ndarray:
+    """The 3x3 dilation of a packed-row support per image and level (bool [N * sum(h * w)])."""
+    out = np.zeros_like(rows, dtype=bool)
+    img = sum(h * w for h, w in shapes)
+    for b in range(N):
+        off = b * img
+        for h, w in shapes:
+            a = rows[off:off + h * w].reshape(h, w).astype(bool)
+            p = np.zeros((h + 2, w + 2), dtype=bool)
+            p[1:-1, 1:-1] = a
+            d = np.zeros((h, w), dtype=bool)
+            for dy in range(3):
+                for dx in range(3):
+                    d |= p[dy:dy + h, dx:dx + w]
+            out[off:off + h * w] = d.reshape(-1)
+            off += h * w
+    return out
+
+
+def active_tiles(tab: np.ndarray, rows: np.ndarray) -> np.ndarray:
+    """bool [ntiles]: a tile is active when any of its boxes, extended by one pixel and clipped to the level, holds a
+    set row of ``rows`` (bool [P], the support of the conv's INPUT) -- exactly the tiles whose halo is not all zero."""
+    act = np.zeros(len(tab), dtype=bool)
+    for i, row in enumerate(tab):
+        for (sbeg, hoff, ib, ob, H, W, y0, x0, R, C) in _boxes(row):
+            ya, yb = max(0, y0 - 1), min(H - 1, y0 + R)
+            xa, xb = max(0, x0 - 1), min(W - 1, x0 + C)
+            lv = rows[ob:ob + H * W].reshape(H, W)
+            if lv[ya:yb + 1, xa:xb + 1].any():
+                act[i] = True
+                break
+    return act
+
+
+def tile_rows(tab: np.ndarray, which: np.ndarray, P: int) -> np.ndarray:
+    """bool [P]: the output rows (slots) of the tiles selected by ``which``."""
+    out = np.zeros(P, dtype=bool)
+    for row in tab[np.asarray(which, dtype=bool)]:
+        for (sbeg, hoff, ib, ob, H, W, y0, x0, R, C) in _boxes(row):
+            for r in range(R):
+                out[ob + (y0 + r) * W + x0:ob + (y0 + r) * W + x0 + C] = True
+    return out
+
+
 _CACHE: Dict[tuple, object] = {}
 
 

@@ -122,6 +122,14 @@ _SIGS = {
                                ctypes.POINTER(ConvGeom), c_int, c_vp],
     "mxr_conv_wgrad_p8_bias": [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp, ctypes.POINTER(ConvGeom),
                                c_int, c_vp, c_int, c_vp],
+    # the sparse regression-gradient forms (csrc/kernels/row_activity.hip, ops/row_activity.py)
+    "mxr_conv3x3_hx32_act": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(ConvGeom), c_vp, c_int, c_int,
+                             c_int, c_int, c_vp, c_vp, c_vp],
+    "mxr_conv_wgrad_p8_bias_act": [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp, ctypes.POINTER(ConvGeom),
+                                   c_int, c_vp, c_int, c_vp, c_vp],
+    "mxr_rows_nonzero": [c_vp, c_ll, c_int, c_vp, c_vp],
+    "mxr_rows_dilate": [c_vp, c_vp, c_int, c_ll, ctypes.POINTER(ConvGeom), c_vp],
+    "mxr_halo_active_tiles": [c_vp, c_int, c_vp, c_ll, c_int, c_vp, c_vp, c_vp],
     "mxr_conv_wgrad_pipe": [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp, ctypes.POINTER(ConvGeom), c_int,
                             c_vp],
     "mxr_conv_wgrad_pipe_direct": [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, ctypes.POINTER(ConvGeom), c_int, c_vp],

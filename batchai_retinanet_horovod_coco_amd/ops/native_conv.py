@@ -24,6 +24,7 @@ import torch.nn.functional as F
 from . import native as _n
 from .native import ConvGeom, _chk, _p, _s, lib, zero_page, c_int, c_ll, c_vp
 from .side_stream import SIDE
+from . import row_activity as _ra
 from .conv_launch import (  # noqa: F401  (re-exported: the public surface of native_conv)
     MASK_BITS, BitMask, bits_capable, proj_fusable, run_fwd_proj, run_fwd_into, C1X1_BN, FWD_VARIANTS, HALO_VARIANTS, HX32_VARIANTS, P8_TUNED, P8_VARIANTS, _BOUND, _SIGS, _bind,
     _effective, _miopen_pyramid_wgrad, _miopen_wgrad, _only, _out_hw, _variant, bias_res_act_,
@@ -396,8 +397,11 @@ class PyramidConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, shapes, relu, mask_input_grad=False, grad_premasked=False, pad_sink=None,
-                join=None, out_f8=False):
+                join=None, out_f8=False, act=None):
         from .conv_tuner import TUNER
+        # act = (row_activity.GradChain, k): this layer is k layers below the regression final, whose backward starts
+        # the chain from the loss gradient's non-zero rows (bf16 heads without a norm: Submodel.forward_packed)
+        ctx.act = act
         x = x.contiguous()
         N, P, cin = x.shape
         cout = weight.shape[0]
@@ -491,6 +495,17 @@ class PyramidConvFn(torch.autograd.Function):
         mk = None
         if mask_in:
             mk = ctx.bits_in if ctx.bits_in is not None else x
+        # the rows of dy that can be non-zero (ops.row_activity): the final derives them from dy itself (the mask
+        # kernels run here, on the compute stream, before the side stream forks for the weight gradient), a tower
+        # layer takes the chain's dilated mask.  The final's weight gradient stays dense: its role-swapped form runs
+        # the im2col over dY (it would need the dilated mask on the K side and X on the other).
+        ract = wact = None
+        if ctx.act is not None and ctx.f8x is None:
+            chain, depth_k = ctx.act
+            if depth_k == 0:
+                chain.start(dy, N, shapes)
+            ract = chain.level(depth_k)
+            wact = ract if depth_k > 0 else None
         f8_only_in = getattr(x, "_mxr_f8only", False)
         from . import fp8 as _f8
         f8dy = None
@@ -539,8 +554,9 @@ class PyramidConvFn(torch.autograd.Function):
                     ctx.join.release()
                     dx = None
             elif buf is None:
-                dx = TUNER.run(key, fwd_candidates(dyp, wd, None, None, gd, 1, (1, 1, 1, 1), False, (N, P, cin),
-                                                   allow_miopen=False, mask=mk))
+                with _ra.using(ract):
+                    dx = TUNER.run(key, fwd_candidates(dyp, wd, None, None, gd, 1, (1, 1, 1, 1), False, (N, P, cin),
+                                                       allow_miopen=False, mask=mk))
                 if ctx.join is not None:
                     ctx.join.buf = dx
             else:
@@ -549,7 +565,8 @@ class PyramidConvFn(torch.autograd.Function):
                 if TUNER.needs_tuning(key + "|a", cands):
                     TUNER.run(key + "|a", fwd_candidates(dyp, wd, None, None, gd, 1, (1, 1, 1, 1), False,
                                                          (N, P, cin), allow_miopen=False, mask=mk, out=buf.clone()))
-                TUNER.run(key + "|a", cands)
+                with _ra.using(ract):
+                    TUNER.run(key + "|a", cands)
                 ctx.join.release()
                 dx = None
         fused_bias = False
@@ -566,9 +583,10 @@ class PyramidConvFn(torch.autograd.Function):
                     dw = dw.to(ctx.wdt)
                 if has_bias and ctx.needs_input_grad[2] and not fb:
                     db = deliver_bias_grad(ctx.params[1], dy, channels=cout)
-                return dx, dw, db, None, None, None, None, None, None, None
-            fused_bias = (has_bias and ctx.needs_input_grad[2]
-                          and deliver_wgrad_bias_fused(wkey, x, dy, gw, ctx.params[0], ctx.params[1]))
+                return dx, dw, db, None, None, None, None, None, None, None, None
+            with _ra.using(wact):
+                fused_bias = (has_bias and ctx.needs_input_grad[2]
+                              and deliver_wgrad_bias_fused(wkey, x, dy, gw, ctx.params[0], ctx.params[1]))
         if f8_only_in and ctx.needs_input_grad[1]:
             raise RuntimeError("PyramidConvFn: a bf16 weight gradient over an fp8-only tower output")
         if ctx.needs_input_grad[1] and not fused_bias:
@@ -593,12 +611,13 @@ class PyramidConvFn(torch.autograd.Function):
                     if only is None:
                         c.update({n: (lambda fn=fn: sink.add_(fn())) for n, fn in narrow.items()})
                     return c
-            dw = _deliver_wgrad(wkey, cands, sink_make, ctx.params[0], (x, dy))
+            with _ra.using(wact):
+                dw = _deliver_wgrad(wkey, cands, sink_make, ctx.params[0], (x, dy))
             if dw is not None:
                 dw = dw.to(ctx.wdt)
         if has_bias and ctx.needs_input_grad[2] and not fused_bias:
             db = deliver_bias_grad(ctx.params[1], dy, channels=cout)
-        return dx, dw, db, None, None, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None, None
 
 def _focal_fused(pad_sink, relu, b, g: ConvGeom, key: str) -> bool:
     """Whether this pyramid layer is the classification final with a focal request and a tuned conv_hx32 variant
@@ -724,13 +743,14 @@ def pyramid_pack(xs: Sequence[torch.Tensor]):
     return packed, shapes
 
 def pyramid_conv_layer(x, shapes, layer, relu, mask_input_grad=False, grad_premasked=False,
-                       pad_sink=None, join=None, out_f8: bool = False) -> torch.Tensor:
+                       pad_sink=None, join=None, out_f8: bool = False, act=None) -> torch.Tensor:
     """``mask_input_grad``: x is a relu output whose only consumer is this layer -> its relu backward
     is fused into this layer's dgrad; ``grad_premasked``: the (sole) consumer of this layer's relu
     output does that, so skip the relu backward here; ``out_f8``: that consumer is an fp8 head layer (under fp8
-    the output may then exist only as its fp8 copy and relu bitmask, ops.fp8.pyramid_forward)."""
+    the output may then exist only as its fp8 copy and relu bitmask, ops.fp8.pyramid_forward); ``act``: the
+    (``row_activity.GradChain``, layers below the final) of a regression tower whose gradient is sparse."""
     return PyramidConvFn.apply(x, layer.weight, layer.bias, tuple(shapes), bool(relu), bool(mask_input_grad),
-                               bool(grad_premasked), pad_sink, join, bool(out_f8))
+                               bool(grad_premasked), pad_sink, join, bool(out_f8), act)
 
 def pyramid_unpack(y, shapes):
     out, off = [], 0

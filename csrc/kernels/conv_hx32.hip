@@ -116,13 +116,19 @@ __device__ __forceinline__ int h2_off(int h, int u) { return (h << 5) + ((u ^ ((
 // FOC (> 0: the class count): the classification final's fused focal loss -- the logits never reach memory; each
 // 8-logit chunk becomes its focal gradient in the padded dY rows (FocalArgs) and a loss term (one partial per block)
 // BW: the plain relu forward also writes its output's bitmask (Mk, pointer bit 0 set): one byte store per chunk
+// ACT: a data gradient whose input is zero outside a known support (row_activity.hip): act_list is a permutation of
+// the tile indices with the *act_cnt ACTIVE tiles first.  Work item i maps to tile act_list[i / tiles_co]; only the
+// items of active tiles run the convolution (the persistent loop bound and the next-tile prefetch follow the list;
+// the count is read on the device).  An inactive tile's whole halo is zero, so its result is +0 everywhere: its
+// output slots get zeros by 16-B stores from the same launch (nothing in the accumulate form).  No bias / residual /
+// relu (the launcher checks).
 template <int BCO, int PERS, int DIAG = 0, int HL = 0, int NWV = 8, int HB1 = 0, int WR3 = 0, int MK = 0, int FOC = 0,
-          int BW = 0, int M16 = 0>
+          int BW = 0, int M16 = 0, int ACT = 0>
 __global__ __launch_bounds__(NWV * 64, (HB1 ? (NWV == 4 ? 3 : 4) : (NWV == 8 ? 2 : 1))) void conv3x3_hx32_kernel(
     const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wt, const float* __restrict__ bias,
     const bf16_t* __restrict__ Rs, const bf16_t* __restrict__ Mk, bf16_t* __restrict__ Y,
     const bf16_t* __restrict__ zpage, const HaloTile* __restrict__ tiles, ConvGeom g, int relu, int accumulate,
-    int tiles_co, int nwork, FocalArgs fa) {
+    int tiles_co, int nwork, FocalArgs fa, const int* __restrict__ act_list, const int* __restrict__ act_cnt) {
   uint8_t* const mkb = (uint8_t*)((uintptr_t)Mk & ~(uintptr_t)1);   // MK = 2 / BW: the bitmask
   constexpr int NW = NWV, WCO = 2, WPX = NW / WCO;
   constexpr int H2_HQ = (H2_HPC + NW - 1) / NW;   // halo pieces per wave per chunk (a piece past 28 repeats one)
@@ -172,12 +178,13 @@ __global__ __launch_bounds__(NWV * 64, (HB1 ? (NWV == 4 ? 3 : 4) : (NWV == 8 ? 2
   // that are never stored).  Halo: piece k = 32 halo rows (k / 2) x plane (k % 2), wave w issues
   // k = w + 8 q; hsrc = element offset of the lane's 16 B in chunk 0, -1 = outside the level.
   auto tile_co0 = [&](int item) { return (item % tiles_co) * BCO; };
+  auto tile_of = [&](int item) { return ACT ? act_list[item / tiles_co] : item / tiles_co; };
   auto w_voff = [&](int co0, int* vo) {   // (pointer params: an array-reference parameter typed by a local constexpr made hipcc drop the kernel host stubs)
 #pragma unroll
     for (int v = 0; v < NVO; ++v) vo[v] = min(co0 + (wg + NW * v) * 32 + (lane >> 1), cout - 1) * 32 + hsub * 16;
   };
   auto decode_halo = [&](int item, int* hs) {
-    const HaloTile& T = tiles[item / tiles_co];
+    const HaloTile& T = tiles[tile_of(item)];
 #pragma unroll
     for (int q = 0; q < H2_HQ; ++q) {
       int k = wave + NW * q;
@@ -209,7 +216,7 @@ __global__ __launch_bounds__(NWV * 64, (HB1 ? (NWV == 4 ? 3 : 4) : (NWV == 8 ? 2
   // results are discarded)
   int hb[TJ], hp[TJ], mo[TJ];
   auto decode_frag = [&](int item) {
-    const HaloTile& T = tiles[item / tiles_co];
+    const HaloTile& T = tiles[tile_of(item)];
 #pragma unroll
     for (int j = 0; j < TJ; ++j) {
       const int p = wpx * WT_PIX + j * MS + (lane & (MS - 1));
@@ -417,6 +424,42 @@ __global__ __launch_bounds__(NWV * 64, (HB1 ? (NWV == 4 ? 3 : 4) : (NWV == 8 ? 2
 
   // ---- first tile: its halo (chunk 0) and weight row (chunk 0, ky 0), its bias
   int item = PERS ? (int)blockIdx.x : xcd_remap(blockIdx.x, gridDim.x);
+  int nwork_c = nwork;   // ACT: the work items of the active tiles come first
+  if constexpr (ACT) {
+    nwork_c = __builtin_amdgcn_readfirstlane(*act_cnt) * tiles_co;
+    // the blocks below nwork_c take the active items (remapped among themselves: the same XCD locality over a
+    // dense share of every XCD), the others one inactive item each
+    if constexpr (!PERS) item = (int)blockIdx.x < nwork_c ? xcd_remap(blockIdx.x, nwork_c) : (int)blockIdx.x;
+    // zeros into the output slots of an inactive tile's item: 16-B chunk ch of slot p per thread
+    auto zero_item = [&](int z) {
+      const HaloTile& T = tiles[tile_of(z)];
+      const int zc0 = tile_co0(z);
+      const int nchk = min(BCO, cout - zc0) >> 3;
+      const int n = T.nslot * nchk;
+      for (int i = threadIdx.x; i < n; i += NW * 64) {
+        const int p = fdiv(i, nchk), ch = i - p * nchk;
+        HX_SELECT(sbeg, p)
+        int sb = T.b[0].sbeg, C = T.b[0].C, ob = T.b[0].out_base, W = T.b[0].W, y0 = T.b[0].y0, x0 = T.b[0].x0;
+#pragma unroll
+        for (int t = 1; t < HX_BOX; ++t)
+          if (sel == t) {
+            sb = T.b[t].sbeg; C = T.b[t].C; ob = T.b[t].out_base; W = T.b[t].W; y0 = T.b[t].y0; x0 = T.b[t].x0;
+          }
+        const int loc = p - sb;
+        const int r = fdiv(loc, C), c = loc - r * C;
+        *reinterpret_cast<uint4*>(Y + (long long)(ob + (y0 + r) * W + x0 + c) * cout + zc0 + ch * 8) =
+            make_uint4(0u, 0u, 0u, 0u);
+      }
+    };
+    if (!accumulate) {
+      if constexpr (PERS) {
+        for (int z = nwork_c + item; z < nwork; z += (int)gridDim.x) zero_item(z);
+      } else if (item >= nwork_c) {
+        zero_item(item);
+      }
+    }
+    if (item >= nwork_c) return;
+  }
   float foc_acc = 0.f, foc_inv = 0.f, foc_elo = 0.f, foc_ehi = 0.f;   // FOC: the block's loss, 1 / #positives
   if constexpr (FOC > 0) {
     foc_inv = 1.0f / fmaxf(1.0f, (float)(*fa.npos));
@@ -443,7 +486,7 @@ __global__ __launch_bounds__(NWV * 64, (HB1 ? (NWV == 4 ? 3 : 4) : (NWV == 8 ? 2
     // the next tile of this block (PERS), its DMA sources decoded now: its halo and first weight row go
     // out during this tile's last chunk (into the buffer / slot that chunk leaves free)
     const int nitem = item + (int)gridDim.x;
-    const bool has_next = PERS && nitem < nwork;
+    const bool has_next = PERS && nitem < nwork_c;
     int nco0 = co0, nwvoff[NVO], nhsrc[H2_HQ];
 #pragma unroll
     for (int v = 0; v < NVO; ++v) nwvoff[v] = wvoff[v];
@@ -718,16 +761,17 @@ __global__ __launch_bounds__(NWV * 64, (HB1 ? (NWV == 4 ? 3 : 4) : (NWV == 8 ? 2
 }
 
 template <int BCO, int PERS, int DIAG = 0, int HL = 0, int NWV = 8, int HB1 = 0, int WR3 = 0, int MK = 0, int FOC = 0,
-          int BW = 0, int M16 = 0>
+          int BW = 0, int M16 = 0, int ACT = 0>
 int launch_hx32(const bf16_t* X, const bf16_t* Wt, const float* bias, const bf16_t* R, const bf16_t* Mk, bf16_t* Y,
                 const bf16_t* zpage, const HaloTile* tiles, int ntiles, const ConvGeom& g, int relu, int accumulate,
-                hipStream_t stream, const FocalArgs& fa = FocalArgs{}) {
+                hipStream_t stream, const FocalArgs& fa = FocalArgs{}, const int* act_list = nullptr,
+                const int* act_cnt = nullptr) {
   const int tiles_co = (g.cout + BCO - 1) / BCO;
   const long long nwork = (long long)tiles_co * ntiles;
   if (nwork > 0x7fffffffLL || nwork < 1) return -3;
   if (PERS && (g.cin / 32) % 2 != 0) return -5;   // the chaining assumes an even chunk count
   const size_t lds = (size_t)(WR3 ? 9 : 6) * BCO * 64 + (HB1 ? 1 : 2) * (size_t)H2_HBYTES + 2 * BCO * 4;
-  auto kern = conv3x3_hx32_kernel<BCO, PERS, DIAG, HL, NWV, HB1, WR3, MK, FOC, BW, M16>;
+  auto kern = conv3x3_hx32_kernel<BCO, PERS, DIAG, HL, NWV, HB1, WR3, MK, FOC, BW, M16, ACT>;
   static bool attr_set = false;
   static int ncu = 0;
   if (!attr_set) {
@@ -741,7 +785,7 @@ int launch_hx32(const bf16_t* X, const bf16_t* Wt, const float* bias, const bf16
   // PERS: one block per CU (the LDS allows no second one), each walking tiles b, b + grid, ...
   const long long grid = PERS ? std::min<long long>(nwork, ncu) : nwork;
   kern<<<(unsigned)grid, NWV * 64, lds, stream>>>(X, Wt, bias, R, Mk, Y, zpage, tiles, g, relu, accumulate, tiles_co,
-                                                    (int)nwork, fa);
+                                                    (int)nwork, fa, act_list, act_cnt);
   return (int)hipGetLastError();
 }
 
@@ -812,6 +856,108 @@ MXR_API int mxr_hx32_pack_weights(const void* W, void* Wp, int cout, int cin, hi
   return (int)hipGetLastError();
 }
 
+namespace {
+
+// launch_hx32<BCO, PERS, DIAG, HL, NWV, HB1, WR3, MK, FOC, BW, M16, ACT> of hx32_dispatch's arguments
+#define HX_LAUNCH(...)                                                                                            \
+  launch_hx32<__VA_ARGS__, ACT>(x, w, bias, r, mk, y, z, t, ntiles, g, relu, accumulate, stream, FocalArgs{}, al, ac)
+
+template <int ACT>
+int hx32_dispatch(const bf16_t* x, const bf16_t* w, const float* bias, const bf16_t* r, const bf16_t* mk, bf16_t* y,
+                  const bf16_t* z, const HaloTile* t, int ntiles, const ConvGeom& g, int relu, int accumulate,
+                  int variant, hipStream_t stream, const int* al, const int* ac) {
+  // the masked data gradient of the winning variants (0, 6) runs the compile-time masked epilogue (bf16 mask or
+  // bitmask), the plain relu forward writing a bitmask its compile-time form (BW)
+  const bool bits = mk != nullptr && ((uintptr_t)mk & 1);
+  const bool mk_fast = mk != nullptr && r == nullptr && !accumulate && !relu;
+  if (mk_fast && variant == 0 && !bits) return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 1, 0, 0, 0);
+  if (mk_fast && variant == 6 && !bits) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 1, 0, 0, 0);
+  if (mk_fast && variant == 0 && bits) return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 2, 0, 0, 0);
+  if (mk_fast && variant == 6 && bits) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 2, 0, 0, 0);
+  if (mk_fast && variant == 10 && !bits) return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 1, 0, 0, 1);
+  if (mk_fast && variant == 10 && bits) return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 2, 0, 0, 1);
+  if (mk_fast && variant == 11 && !bits) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 1, 0, 0, 1);
+  if (mk_fast && variant == 11 && bits) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 2, 0, 0, 1);
+  if constexpr (!ACT) {
+    const bool bw_fast = bits && relu && r == nullptr && !accumulate;
+    if (bw_fast && variant == 0) return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 0, 0, 1, 0);
+    if (bw_fast && variant == 6) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 0, 0, 1, 0);
+    if (bw_fast && variant == 10) return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 0, 0, 1, 1);
+    if (bw_fast && variant == 11) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 0, 0, 1, 1);
+  }
+  switch (variant) {
+    case 0: return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 0, 0, 0, 0);
+    case 1: return HX_LAUNCH(128, 0, 0, 0, 8, 0, 0, 0, 0, 0, 0);
+    case 2: return HX_LAUNCH(256, 1, 0, 0, 8, 0, 0, 0, 0, 0, 0);
+    case 3: return HX_LAUNCH(128, 1, 0, 0, 8, 0, 0, 0, 0, 0, 0);
+    case 4: return HX_LAUNCH(256, 0, 0, 1, 8, 0, 0, 0, 0, 0, 0);
+    case 5: return HX_LAUNCH(128, 0, 0, 1, 8, 0, 0, 0, 0, 0, 0);
+    case 6: return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 0, 0, 0, 0);
+    case 7: return HX_LAUNCH(128, 0, 0, 0, 8, 0, 1, 0, 0, 0, 0);
+    // 64-channel tiles for the narrow layers (the 64-padded regression final, the stage-2 64 -> 64 convs): 4 waves
+    // (2 co x 2 px, 32 x 128 per wave); 9 with one halo buffer (53 KiB: three blocks share a CU)
+    case 8: return HX_LAUNCH(64, 0, 0, 0, 4, 0, 0, 0, 0, 0, 0);
+    case 9: return HX_LAUNCH(64, 0, 0, 0, 4, 1, 0, 0, 0, 0, 0);
+    // 10 / 11 / 12: variants 0 / 6 / 1 on the 16x16x32 MFMA (M16: unswizzled plane images, one K = 32 step per tap)
+    case 10: return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 0, 0, 0, 1);
+    case 11: return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 0, 0, 0, 1);
+    case 12: return HX_LAUNCH(128, 0, 0, 0, 8, 0, 0, 0, 0, 0, 1);
+    // 13 / 14 / 15: the persistent grids 2 / 3 and the three-slot weight ring 7 on the 16x16x32 MFMA
+    case 13: return HX_LAUNCH(256, 1, 0, 0, 8, 0, 0, 0, 0, 0, 1);
+    case 14: return HX_LAUNCH(128, 1, 0, 0, 8, 0, 0, 0, 0, 0, 1);
+    case 15: return HX_LAUNCH(128, 0, 0, 0, 8, 0, 1, 0, 0, 0, 1);
+    // (the 64-channel tiles on the 16x16x32 MFMA measured 6 % faster than variant 8 but 10 % slower than 9 -- its
+    // one-halo-buffer form spills at 168 VGPRs: profiles/r6_hx32_m16_ab.txt; not built)
+    default: break;
+  }
+#ifdef MXR_DIAG_KERNELS   // timing-only builds: _lib/diag/libmxr_kernels.so (build.py --diag), never the production library
+  if constexpr (!ACT) {
+    switch (variant) {
+      case 101: return HX_LAUNCH(256, 1, 1, 0, 8, 0, 0, 0, 0, 0, 0);
+      case 102: return HX_LAUNCH(256, 1, 2, 0, 8, 0, 0, 0, 0, 0, 0);
+      case 103: return HX_LAUNCH(256, 1, 3, 0, 8, 0, 0, 0, 0, 0, 0);
+      case 108: return HX_LAUNCH(256, 1, 8, 0, 8, 0, 0, 0, 0, 0, 0);
+      case 111: return HX_LAUNCH(256, 1, 11, 0, 8, 0, 0, 0, 0, 0, 0);
+      case 132: return HX_LAUNCH(256, 0, 32, 0, 8, 0, 0, 0, 0, 0, 0);
+      case 116: return HX_LAUNCH(256, 0, 16, 0, 8, 0, 0, 0, 0, 0, 0);
+      case 126: return HX_LAUNCH(128, 0, 16, 0, 8, 1, 0, 0, 0, 0, 0);
+      // bit 6: every 32x32x16 MFMA as two 16x16x32 on the same operands (same FLOPs; the shape's sustained clock)
+      case 164: return HX_LAUNCH(256, 0, 64, 0, 8, 0, 0, 0, 0, 0, 0);
+      case 170: return HX_LAUNCH(128, 0, 64, 0, 8, 1, 0, 0, 0, 0, 0);
+      default: break;
+    }
+  }
+#endif
+  return -6;
+}
+#undef HX_LAUNCH
+
+}  // namespace
+
+// act_list / act_cnt (optional, both or neither): a data gradient over an input that is zero outside the support the
+// list was built from (mxr_halo_active_tiles over the same tile table): only the listed active tiles are computed,
+// the others get zeros (nothing when accumulating).  Requires no bias, residual or relu.
+MXR_API int mxr_conv3x3_hx32_act(const void* X, const void* Wt, const float* bias, const void* R, const void* Mk,
+                                 void* Y, const void* zpage, const ConvGeom* g, const void* tiles, int ntiles, int relu,
+                                 int accumulate, int variant, const int* act_list, const int* act_cnt,
+                                 hipStream_t stream) {
+  if (g->cin % 32 != 0 || g->cout % 8 != 0) return -1;
+  if (g->kh != 3 || g->kw != 3 || g->stride != 1 || g->pt != 1 || g->pl != 1 || g->ostride != 1) return -2;
+  if (g->in_img != g->out_img || (g->M + 1) * (long long)std::max(g->cin, g->cout) >= (1LL << 31)) return -4;
+  if ((long long)g->cout * 9 * g->cin * 2 >= (1LL << 31)) return -4;
+  const bf16_t *x = (const bf16_t*)X, *w = (const bf16_t*)Wt, *r = (const bf16_t*)R, *mk = (const bf16_t*)Mk;
+  const bf16_t* z = (const bf16_t*)zpage;
+  const HaloTile* t = (const HaloTile*)tiles;
+  bf16_t* y = (bf16_t*)Y;
+  if ((act_list == nullptr) != (act_cnt == nullptr)) return -7;
+  if (act_list != nullptr) {
+    if (bias != nullptr || r != nullptr || relu) return -7;
+    return hx32_dispatch<1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, variant, stream, act_list,
+                            act_cnt);
+  }
+  return hx32_dispatch<0>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, variant, stream, nullptr, nullptr);
+}
+
 // variant: 0 = 256 co x 256 px (154 KiB LDS), 1 = 128 co x 256 px (105 KiB), 2 / 3 = the same on a
 // persistent grid (even chunk count only), 4 / 5 = 0 / 1 with 64-B halo rows (HL 1), 6 = 1 with one halo
 // buffer (77 KiB, two blocks per CU), 7 = 1 with a three-slot weight ring fetched two stages ahead (129 KiB).
@@ -827,81 +973,8 @@ MXR_API int mxr_hx32_pack_weights(const void* W, void* Wp, int cout, int cin, hi
 MXR_API int mxr_conv3x3_hx32(const void* X, const void* Wt, const float* bias, const void* R, const void* Mk,
                              void* Y, const void* zpage, const ConvGeom* g, const void* tiles, int ntiles, int relu,
                              int accumulate, int variant, hipStream_t stream) {
-  if (g->cin % 32 != 0 || g->cout % 8 != 0) return -1;
-  if (g->kh != 3 || g->kw != 3 || g->stride != 1 || g->pt != 1 || g->pl != 1 || g->ostride != 1) return -2;
-  if (g->in_img != g->out_img || (g->M + 1) * (long long)std::max(g->cin, g->cout) >= (1LL << 31)) return -4;
-  if ((long long)g->cout * 9 * g->cin * 2 >= (1LL << 31)) return -4;
-  const bf16_t *x = (const bf16_t*)X, *w = (const bf16_t*)Wt, *r = (const bf16_t*)R, *mk = (const bf16_t*)Mk;
-  const bf16_t* z = (const bf16_t*)zpage;
-  const HaloTile* t = (const HaloTile*)tiles;
-  bf16_t* y = (bf16_t*)Y;
-  // the masked data gradient of the winning variants (0, 6) runs the compile-time masked epilogue (bf16 mask or
-  // bitmask), the plain relu forward writing a bitmask its compile-time form (BW)
-  const bool bits = mk != nullptr && ((uintptr_t)mk & 1);
-  const bool mk_fast = mk != nullptr && r == nullptr && !accumulate && !relu;
-  if (mk_fast && variant == 0 && !bits)
-    return launch_hx32<256, 0, 0, 0, 8, 0, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-  if (mk_fast && variant == 6 && !bits)
-    return launch_hx32<128, 0, 0, 0, 8, 1, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-  if (mk_fast && variant == 0 && bits)
-    return launch_hx32<256, 0, 0, 0, 8, 0, 0, 2>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-  if (mk_fast && variant == 6 && bits)
-    return launch_hx32<128, 0, 0, 0, 8, 1, 0, 2>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-  if (mk_fast && variant == 10 && !bits)
-    return launch_hx32<256, 0, 0, 0, 8, 0, 0, 1, 0, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-  if (mk_fast && variant == 10 && bits)
-    return launch_hx32<256, 0, 0, 0, 8, 0, 0, 2, 0, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-  if (mk_fast && variant == 11 && !bits)
-    return launch_hx32<128, 0, 0, 0, 8, 1, 0, 1, 0, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-  if (mk_fast && variant == 11 && bits)
-    return launch_hx32<128, 0, 0, 0, 8, 1, 0, 2, 0, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-  const bool bw_fast = bits && relu && r == nullptr && !accumulate;
-  if (bw_fast && variant == 0)
-    return launch_hx32<256, 0, 0, 0, 8, 0, 0, 0, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-  if (bw_fast && variant == 6)
-    return launch_hx32<128, 0, 0, 0, 8, 1, 0, 0, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-  if (bw_fast && variant == 10)
-    return launch_hx32<256, 0, 0, 0, 8, 0, 0, 0, 0, 1, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-  if (bw_fast && variant == 11)
-    return launch_hx32<128, 0, 0, 0, 8, 1, 0, 0, 0, 1, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-  switch (variant) {
-    case 0: return launch_hx32<256, 0>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 1: return launch_hx32<128, 0>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 2: return launch_hx32<256, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 3: return launch_hx32<128, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 4: return launch_hx32<256, 0, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 5: return launch_hx32<128, 0, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 6: return launch_hx32<128, 0, 0, 0, 8, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 7: return launch_hx32<128, 0, 0, 0, 8, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    // 64-channel tiles for the narrow layers (the 64-padded regression final, the stage-2 64 -> 64 convs): 4 waves
-    // (2 co x 2 px, 32 x 128 per wave); 9 with one halo buffer (53 KiB: three blocks share a CU)
-    case 8: return launch_hx32<64, 0, 0, 0, 4>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 9: return launch_hx32<64, 0, 0, 0, 4, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    // 10 / 11 / 12: variants 0 / 6 / 1 on the 16x16x32 MFMA (M16: unswizzled plane images, one K = 32 step per tap)
-    case 10: return launch_hx32<256, 0, 0, 0, 8, 0, 0, 0, 0, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 11: return launch_hx32<128, 0, 0, 0, 8, 1, 0, 0, 0, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 12: return launch_hx32<128, 0, 0, 0, 8, 0, 0, 0, 0, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    // 13 / 14 / 15: the persistent grids 2 / 3 and the three-slot weight ring 7 on the 16x16x32 MFMA
-    case 13: return launch_hx32<256, 1, 0, 0, 8, 0, 0, 0, 0, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 14: return launch_hx32<128, 1, 0, 0, 8, 0, 0, 0, 0, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 15: return launch_hx32<128, 0, 0, 0, 8, 0, 1, 0, 0, 0, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    // (the 64-channel tiles on the 16x16x32 MFMA measured 6 % faster than variant 8 but 10 % slower than 9 -- its
-    // one-halo-buffer form spills at 168 VGPRs: profiles/r6_hx32_m16_ab.txt; not built)
-#ifdef MXR_DIAG_KERNELS   // timing-only builds: _lib/diag/libmxr_kernels.so (build.py --diag), never the production library
-    case 101: return launch_hx32<256, 1, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 102: return launch_hx32<256, 1, 2>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 103: return launch_hx32<256, 1, 3>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 108: return launch_hx32<256, 1, 8>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 111: return launch_hx32<256, 1, 11>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 132: return launch_hx32<256, 0, 32>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 116: return launch_hx32<256, 0, 16>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 126: return launch_hx32<128, 0, 16, 0, 8, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    // bit 6: every 32x32x16 MFMA as two 16x16x32 on the same operands (same FLOPs; the shape's sustained clock)
-    case 164: return launch_hx32<256, 0, 64>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-    case 170: return launch_hx32<128, 0, 64, 0, 8, 1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, stream);
-#endif
-    default: return -6;
-  }
+  return mxr_conv3x3_hx32_act(X, Wt, bias, R, Mk, Y, zpage, g, tiles, ntiles, relu, accumulate, variant, nullptr,
+                              nullptr, stream);
 }
 
 void mxr_loss_finalize_launch(const float* partials, int n, const int* npos, float* out, hipStream_t stream);

@@ -44,6 +44,12 @@ constexpr int WQ_NW = 8;
 constexpr int WQ_HB = 64 * 256;                 // one half image: 64 pixel rows x 256 B
 constexpr int WQ_BUF = 4 * WQ_HB;               // U0 U1 T0 T1
 constexpr int WQ_LDS = 2 * WQ_BUF + 6 * MXR_MAXLEV * 4;
+// SP: one bit per K-tile of the block's split range (set: the tile's dY rows are not all zero), behind the level
+// tables; a split may span WQ_TBW * 64 K-tiles
+constexpr int WQ_TBW = 64;
+constexpr int WQ_TBOFF = 2 * WQ_BUF + 128;
+constexpr int WQ_LDS_SP = WQ_TBOFF + WQ_TBW * 8;
+static_assert(WQ_TBOFF >= WQ_LDS && WQ_TBOFF % 8 == 0, "tile bits behind the level tables");
 
 __device__ __forceinline__ s16x4 wq_tr(const char* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
@@ -61,11 +67,16 @@ __device__ __forceinline__ void wq_vm_wait() {
 // DS: dual-source weight gradient of a projection block (branch2c + branch1 over ONE read of dY):
 // dW[co, k] for k < k1 over X1 = the branch2b output [M, k1] (row m of the output grid), for k >= k1 over the 1x1
 // stride-s im2col of X (g: the branch1 geometry, g.cin = K - k1); K = Kt; the slab row holds both weight matrices.
-template <int PRIO, int RF = 0, int BIAS = 0, int OPQ = 0, int DS = 0>
+// SP: rowmask (one bit per dY row, word t = K-tile t: row_activity.hip) marks the rows of dY that are not all zero;
+// within its split range [t_begin, t_end) the block visits only the K-tiles whose word is non-zero.  A skipped
+// K-tile would add +-0 products to accumulators that start at +0 and cannot become -0, so the slabs (and the bias
+// partials) are bit-identical to the dense walk; a block without an active K-tile writes its zero slab.
+template <int PRIO, int RF = 0, int BIAS = 0, int OPQ = 0, int DS = 0, int SP = 0>
 __global__ __launch_bounds__(WQ_NW * 64, 2) void conv_wgrad_p8_kernel(
     const bf16_t* __restrict__ X, const bf16_t* __restrict__ dY, int ldy, float* __restrict__ part,
     float* __restrict__ bpart, const bf16_t* __restrict__ zpage, ConvGeom g, int tiles_k, int tiles_co, int splits,
-    int ntm, const bf16_t* __restrict__ X1, int k1, int Kt) {
+    int ntm, const bf16_t* __restrict__ X1, int k1, int Kt, const unsigned long long* __restrict__ rowmask) {
+  static_assert(!(SP && DS), "row mask: the single-source forms");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -85,7 +96,34 @@ __global__ __launch_bounds__(WQ_NW * 64, 2) void conv_wgrad_p8_kernel(
     const int* src = a == 0 ? g.H : a == 1 ? g.W : a == 2 ? g.Ho : a == 3 ? g.Wo : a == 4 ? g.in_off : g.mstart;
     lt[threadIdx.x] = src[t];
   }
+  // SP: bit i of tb = K-tile t_begin + i is active (wave w's ballot is word w + 8 j; zero past t_end)
+  unsigned long long* tb = reinterpret_cast<unsigned long long*>(smem + WQ_TBOFF);
+  if constexpr (SP) {
+#pragma unroll 1
+    for (int j = 0; j < WQ_TBW / WQ_NW; ++j) {
+      const int t = t_begin + j * (WQ_NW * 64) + (int)threadIdx.x;
+      const unsigned long long bal = __ballot(t < t_end && rowmask[t] != 0ull);
+      if (lane == 0) tb[j * WQ_NW + wave] = bal;
+    }
+  }
   __syncthreads();
+  // the first active K-tile at or after n inside the split range (t_end: none); wave-uniform, in SGPRs
+  auto next_active = [&](int n) {
+    const int len = t_end - t_begin;
+    int r = n - t_begin;
+    while (r < len) {
+      const unsigned long long w = tb[r >> 6];
+      const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)w);
+      const unsigned int hi = __builtin_amdgcn_readfirstlane((unsigned int)(w >> 32));
+      const unsigned long long v = (((unsigned long long)hi << 32) | lo) >> (r & 63);
+      if (v) {
+        r += __builtin_ctzll(v);
+        break;
+      }
+      r = (r | 63) + 1;
+    }
+    return t_begin + (r < len ? r : len);
+  };
 
   // ---- DMA slots: piece s (0, 1) of every half = rows 4 (wave + 8 s) + lane / 16, LDS chunk lane % 16
   const int pos = lane & 15;
@@ -118,9 +156,34 @@ __global__ __launch_bounds__(WQ_NW * 64, 2) void conv_wgrad_p8_kernel(
   }
   // the lane's two pixel rows, advanced by 64 per K-tile
   int p_m[2], p_oy[2], p_ox[2], p_l[2], p_img[2], p_H[2], p_W[2], p_Ho[2], p_Wo[2], p_off[2];
+  int n_t = SP ? next_active(t_begin) : t_begin;   // K-tile being issued
+  // SP: the cursor of pixel row m = 64 t + rrow[s] decoded from scratch (a jump over skipped K-tiles); 32-bit:
+  // M + 128 < 2^31
+  auto jump = [&](int s, int t) {
+    const unsigned int m = (unsigned int)t * 64u + (unsigned int)rrow[s];
+    p_m[s] = (int)m;
+    unsigned int b = 0, q = 0;
+    int l = 0;
+    if ((long long)m < g.M) {
+      b = m / (unsigned int)g.out_img;
+      q = m - b * (unsigned int)g.out_img;
+      for (int u = 1; u < g.nlev; ++u)
+        if ((int)q >= lt[5 * MXR_MAXLEV + u]) l = u;
+    }
+    const unsigned int loc = q - (unsigned int)lt[5 * MXR_MAXLEV + l];
+    p_l[s] = l;
+    p_img[s] = (int)b * g.in_img;
+    p_H[s] = lt[l];
+    p_W[s] = lt[MXR_MAXLEV + l];
+    p_Ho[s] = lt[2 * MXR_MAXLEV + l];
+    p_Wo[s] = lt[3 * MXR_MAXLEV + l];
+    p_off[s] = lt[4 * MXR_MAXLEV + l];
+    p_oy[s] = (int)(loc / (unsigned int)p_Wo[s]);
+    p_ox[s] = (int)(loc - (unsigned int)p_oy[s] * (unsigned int)p_Wo[s]);
+  };
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    const long long m = (long long)t_begin * 64 + rrow[s];
+    const long long m = (long long)n_t * 64 + rrow[s];
     p_m[s] = (int)m;
     int b = 0, q = 0, l = 0;
     if (m < g.M) {
@@ -141,10 +204,10 @@ __global__ __launch_bounds__(WQ_NW * 64, 2) void conv_wgrad_p8_kernel(
     p_ox[s] = loc - p_oy[s] * p_Wo[s];
   }
 
-  int n_t = t_begin;   // K-tile being issued
+  int n_is = 0;   // SP: K-tiles issued so far (the buffer parity; dense: n_t - t_begin)
   // hx = 0 U-half 0, 1 T-half 0, 2 T-half 1, 3 U-half 1 of K-tile n_t into buffer (n_t - t_begin) & 1
   auto issue_half = [&](int hx) {
-    char* buf = smem + ((n_t - t_begin) & 1) * WQ_BUF;
+    char* buf = smem + ((SP ? n_is : n_t - t_begin) & 1) * WQ_BUF;
     const bool live = n_t < t_end;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -170,7 +233,21 @@ __global__ __launch_bounds__(WQ_NW * 64, 2) void conv_wgrad_p8_kernel(
       else glds16((const void*)a, dst);
     }
     if (hx == 3) {
-      ++n_t;
+      if constexpr (SP) {
+        // the next active K-tile; a jump re-decodes the cursors (rare next to the 64 MFMAs of a K-tile, and its
+        // temporaries live only inside the branch)
+        const int nn = next_active(n_t + 1);
+        const bool jumped = nn != n_t + 1;
+        n_t = nn;
+        ++n_is;
+        if (jumped) {
+          jump(0, nn);
+          jump(1, nn);
+          return;
+        }
+      } else {
+        ++n_t;
+      }
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         p_m[s] += 64;
@@ -269,10 +346,13 @@ __global__ __launch_bounds__(WQ_NW * 64, 2) void conv_wgrad_p8_kernel(
     asm volatile("" ::: "memory");
   };
 
+  const int n_t_first = n_t;
 #pragma unroll
   for (int hx = 0; hx < 4; ++hx) issue_half(hx);
-  for (int t = t_begin; t < t_end; ++t) {
-    const char* buf = smem + ((t - t_begin) & 1) * WQ_BUF;
+  // (SP: t walks the active K-tiles; n_t is one active tile ahead of it)
+  for (int t = SP ? n_t_first : t_begin, it = 0; t < t_end; ++it) {
+    const char* buf = smem + (it & 1) * WQ_BUF;
+    const int t_next = SP ? n_t : t + 1;
     bf16x8 fa0[4][2], fa1[4][2], fb0[2][2], fb1[2][2];
     // phase 0: U-half 0 + T-half 0
     wq_vm_wait<4>();
@@ -302,6 +382,7 @@ __global__ __launch_bounds__(WQ_NW * 64, 2) void conv_wgrad_p8_kernel(
     issue_half(3);
     mma(fa1, fb0, 4, 0);
     if constexpr (BIAS) colsum(fb0, 0);
+    t = t_next;
   }
   wq_vm_wait<0>();
 
@@ -332,13 +413,25 @@ __global__ __launch_bounds__(WQ_NW * 64, 2) void conv_wgrad_p8_kernel(
 
 template <int PRIO, int RF = 0, int BIAS = 0, int OPQ = 0>
 int launch_wq(const bf16_t* X, const bf16_t* dY, int ldy, float* part, float* bpart, int splits,
-              const bf16_t* zpage, const ConvGeom& g, hipStream_t stream) {
+              const bf16_t* zpage, const ConvGeom& g, const unsigned long long* rowmask, hipStream_t stream) {
   const int K = g.kh * g.kw * g.cin;
   const int tiles_k = (K + 255) / 256;
   const int tiles_co = (g.cout + 255) / 256;
   const long long ntm = (g.M + 63) / 64;
   if (ntm > 0x7fffffffLL) return -4;
   const long long nwg = (long long)tiles_k * tiles_co * splits;
+  // the row mask: only where a split's K-tile range fits the block's tile bits (else the same walk, dense)
+  if (rowmask != nullptr && (ntm + splits - 1) / splits + 1 <= (long long)WQ_TBW * 64) {
+    auto kern = conv_wgrad_p8_kernel<PRIO, RF, BIAS, OPQ, 0, 1>;
+    static bool attr_set = false;
+    if (!attr_set) {
+      hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, WQ_LDS_SP);
+      attr_set = true;
+    }
+    kern<<<(unsigned)nwg, WQ_NW * 64, WQ_LDS_SP, stream>>>(X, dY, ldy, part, bpart, zpage, g, tiles_k, tiles_co, splits,
+                                                           (int)ntm, nullptr, 0, K, rowmask);
+    return (int)hipGetLastError();
+  }
   auto kern = conv_wgrad_p8_kernel<PRIO, RF, BIAS, OPQ>;
   static bool attr_set = false;
   if (!attr_set) {
@@ -346,7 +439,7 @@ int launch_wq(const bf16_t* X, const bf16_t* dY, int ldy, float* part, float* bp
     attr_set = true;
   }
   kern<<<(unsigned)nwg, WQ_NW * 64, WQ_LDS, stream>>>(X, dY, ldy, part, bpart, zpage, g, tiles_k, tiles_co, splits,
-                                                      (int)ntm, nullptr, 0, K);
+                                                      (int)ntm, nullptr, 0, K, nullptr);
   return (int)hipGetLastError();
 }
 
@@ -366,7 +459,7 @@ int launch_wq_dual(const bf16_t* X, const bf16_t* X1, int k1, const bf16_t* dY, 
     attr_set = true;
   }
   kern<<<(unsigned)nwg, WQ_NW * 64, WQ_LDS, stream>>>(X, dY, ldy, part, nullptr, zpage, g, tiles_k, tiles_co, splits,
-                                                      (int)ntm, X1, k1, Kt);
+                                                      (int)ntm, X1, k1, Kt, nullptr);
   return (int)hipGetLastError();
 }
 
@@ -374,14 +467,15 @@ int launch_wq_dual(const bf16_t* X, const bf16_t* X1, int k1, const bf16_t* dY, 
 
 template <int BIAS>
 int launch_wq_variant(const bf16_t* x, const bf16_t* dy, int ldy, float* part, float* bpart, int splits,
-                      const bf16_t* z, const ConvGeom& g, int variant, hipStream_t stream) {
+                      const bf16_t* z, const ConvGeom& g, int variant, const unsigned long long* rowmask,
+                      hipStream_t stream) {
   switch (variant) {
-    case 1: return launch_wq<1, 0, BIAS>(x, dy, ldy, part, bpart, splits, z, g, stream);
-    case 2: return launch_wq<0, 1, BIAS>(x, dy, ldy, part, bpart, splits, z, g, stream);
-    case 3: return launch_wq<1, 1, BIAS>(x, dy, ldy, part, bpart, splits, z, g, stream);
-    case 4: return launch_wq<0, 0, BIAS, 1>(x, dy, ldy, part, bpart, splits, z, g, stream);
-    case 5: return launch_wq<1, 1, BIAS, 1>(x, dy, ldy, part, bpart, splits, z, g, stream);
-    default: return launch_wq<0, 0, BIAS>(x, dy, ldy, part, bpart, splits, z, g, stream);
+    case 1: return launch_wq<1, 0, BIAS>(x, dy, ldy, part, bpart, splits, z, g, rowmask, stream);
+    case 2: return launch_wq<0, 1, BIAS>(x, dy, ldy, part, bpart, splits, z, g, rowmask, stream);
+    case 3: return launch_wq<1, 1, BIAS>(x, dy, ldy, part, bpart, splits, z, g, rowmask, stream);
+    case 4: return launch_wq<0, 0, BIAS, 1>(x, dy, ldy, part, bpart, splits, z, g, rowmask, stream);
+    case 5: return launch_wq<1, 1, BIAS, 1>(x, dy, ldy, part, bpart, splits, z, g, rowmask, stream);
+    default: return launch_wq<0, 0, BIAS>(x, dy, ldy, part, bpart, splits, z, g, rowmask, stream);
   }
 }
 
@@ -389,9 +483,12 @@ int launch_wq_variant(const bf16_t* x, const bf16_t* dy, int ldy, float* part, f
 // (without / with s_setprio); 4 / 5: 0 / 3 with the DMA as inline asm (glds16_asm).  part: splits * cout * K floats (+ splits * cout for the bias partials when
 // bias_out is given: db = sum_m dY[m, :cout], unscaled, into bias_out, accumulated when bias_accumulate).
 // Requires cin % 8 == 0, ldy % 8 == 0, ostride == 1 (and cout % 4 == 0 with bias_out).
-MXR_API int mxr_conv_wgrad_p8_bias(const void* X, const void* dY, int ldy, float* part, int splits, float* out,
-                                   const float* scale, int accumulate, const void* zpage, const ConvGeom* g,
-                                   int variant, float* bias_out, int bias_accumulate, hipStream_t stream) {
+// rowmask (optional): one bit per dY row, set where the row is not all zero (mxr_rows_nonzero, or any superset);
+// K-tiles whose 64 rows are all clear are skipped -- the result is bit-identical to the dense walk.
+MXR_API int mxr_conv_wgrad_p8_bias_act(const void* X, const void* dY, int ldy, float* part, int splits, float* out,
+                                       const float* scale, int accumulate, const void* zpage, const ConvGeom* g,
+                                       int variant, float* bias_out, int bias_accumulate, const void* rowmask,
+                                       hipStream_t stream) {
   if (g->cin % 8 != 0 || ldy % 8 != 0 || g->ostride != 1) return -1;
   if (g->nlev < 1 || g->nlev > MXR_MAXLEV) return -2;
   if (g->M + 128 >= (1LL << 31)) return -4;
@@ -399,13 +496,21 @@ MXR_API int mxr_conv_wgrad_p8_bias(const void* X, const void* dY, int ldy, float
   const bf16_t *x = (const bf16_t*)X, *dy = (const bf16_t*)dY, *z = (const bf16_t*)zpage;
   const int K = g->kh * g->kw * g->cin;
   float* bpart = bias_out ? part + (long long)splits * g->cout * K : nullptr;
-  const int rc = bias_out ? launch_wq_variant<1>(x, dy, ldy, part, bpart, splits, z, *g, variant, stream)
-                          : launch_wq_variant<0>(x, dy, ldy, part, nullptr, splits, z, *g, variant, stream);
+  const unsigned long long* rm = (const unsigned long long*)rowmask;
+  const int rc = bias_out ? launch_wq_variant<1>(x, dy, ldy, part, bpart, splits, z, *g, variant, rm, stream)
+                          : launch_wq_variant<0>(x, dy, ldy, part, nullptr, splits, z, *g, variant, rm, stream);
   if (rc) return rc;
   mxr_wgrad_reduce_launch(part, splits, (long long)g->cout * K, K, scale, out, accumulate, stream);
   // the bias partials: one "row" of cout values (K past any index -> no per-row scale lookup)
   if (bias_out) mxr_wgrad_reduce_launch(bpart, splits, g->cout, 1 << 30, nullptr, bias_out, bias_accumulate, stream);
   return (int)hipGetLastError();
+}
+
+MXR_API int mxr_conv_wgrad_p8_bias(const void* X, const void* dY, int ldy, float* part, int splits, float* out,
+                                   const float* scale, int accumulate, const void* zpage, const ConvGeom* g,
+                                   int variant, float* bias_out, int bias_accumulate, hipStream_t stream) {
+  return mxr_conv_wgrad_p8_bias_act(X, dY, ldy, part, splits, out, scale, accumulate, zpage, g, variant, bias_out,
+                                    bias_accumulate, nullptr, stream);
 }
 
 MXR_API int mxr_conv_wgrad_p8(const void* X, const void* dY, int ldy, float* part, int splits, float* out,
