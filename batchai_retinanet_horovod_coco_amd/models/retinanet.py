@@ -111,13 +111,14 @@ class Submodel(nn.Module):
         w, b = self.final.effective(x[0].dtype)
         return conv_ops.pyramid_conv(x, w, b, relu=False)
 
-    def forward_packed(self, x: torch.Tensor, shapes, pad_sink=None, join=None, chain=None) -> torch.Tensor:
+    def forward_packed(self, x: torch.Tensor, shapes, pad_sink=None, join=None, chain=None, fwd=None) -> torch.Tensor:
         """All 5 levels as ONE ragged GEMM per layer on packed [B, P, C] features.
 
         ``pad_sink``: dict through which the loss may hand the final layer its gradient already in
         zero-padded rows (see :attr:`RetinaNet.cls_pad_sink`); ``chain``: the ``ops.row_activity.GradChain`` of a
         tower whose loss gradient is sparse (the regression submodel; bf16 without a norm -- a norm's backward
-        makes the gradient dense)."""
+        makes the gradient dense); ``fwd``: the ``ops.row_activity.FwdChain`` of a forward whose output is read on
+        positive anchors only (same conditions)."""
         from ..ops import native_conv
         from ..ops import fp8
         if self.norms is not None:
@@ -140,9 +141,11 @@ class Submodel(nn.Module):
             x = native_conv.pyramid_conv_layer(x, shapes, c, True, mask_input_grad=i > 0, grad_premasked=True,
                                                join=join if i == 0 else None,
                                                out_f8=fp8.eligible(nxt.cin, nxt.cout),
-                                               act=None if chain is None else (chain, len(self.tower) - i))
+                                               act=None if chain is None else (chain, len(self.tower) - i),
+                                               need=None if fwd is None else fwd.need(len(self.tower) - i))
         return native_conv.pyramid_conv_layer(x, shapes, self.final, False, mask_input_grad=True,
-                                              pad_sink=pad_sink, act=None if chain is None else (chain, 0))
+                                              pad_sink=pad_sink, act=None if chain is None else (chain, 0),
+                                              need=None if fwd is None else fwd.need(0))
 
     def convs(self) -> List[Conv2D]:
         return list(self.tower) + [self.final]
@@ -220,11 +223,24 @@ class RetinaNet(nn.Module):
             # the regression loss has a gradient on positive anchors only: its tower's backward skips the tiles
             # that multiply zeros (ops.row_activity; MXR_SPARSE_REG_GRAD=0: dense)
             from ..ops import fp8, row_activity
-            chain = None
-            if (torch.is_grad_enabled() and row_activity.enabled() and packed.dtype == torch.bfloat16
-                    and self.head_norm is None and not fp8.enabled()):
-                chain = row_activity.GradChain(len(self.regression_submodel.tower))
-            reg = self.regression_submodel.forward_packed(packed, shapes, self.reg_pad_sink, join=join, chain=chain)
+            chain = fwd = None
+            if (torch.is_grad_enabled() and packed.dtype == torch.bfloat16 and self.head_norm is None
+                    and not fp8.enabled()):
+                depth = len(self.regression_submodel.tower)
+                # the loss reads the regression output on positive anchors only: with the Trainer's request (this
+                # step's anchor states, handed over only when its losses read the output that way) the tower's
+                # FORWARD runs over the tiles that hold a needed row (MXR_SPARSE_REG_FWD=0: dense), and the backward
+                # takes that chain's masks.  No request -- prediction, forward_losses, a plain model(x): dense.
+                state = getattr(self, "positive_request", None)
+                if state is not None and row_activity.fwd_enabled():
+                    fwd = row_activity.FwdChain(depth)
+                    fwd.start(state, self.num_anchors, B, shapes)
+                    if fwd.acts is None:
+                        fwd = None
+                if row_activity.enabled():
+                    chain = row_activity.GradChain(depth, fwd=fwd)
+            reg = self.regression_submodel.forward_packed(packed, shapes, self.reg_pad_sink, join=join, chain=chain,
+                                                          fwd=fwd)
             # The classification final layer's data gradient runs on 64-padded rows (720 -> 768): a
             # loss kernel may write its gradient there directly (Trainer._losses_backward) instead of
             # autograd handing over (B, A, 80) rows that then get padded -- one 0.5 GB copy per step.

@@ -279,7 +279,9 @@ def launch_hx32(x, w, bias, res, y, g: ConvGeom, relu: bool, accumulate: bool = 
     images (csrc/kernels/conv_hx32.hip; same tile table as :func:`launch_halo`).
     ``active`` (an ``ops.row_activity.Activity``; default: the one of the enclosing ``row_activity.using`` block): a
     data gradient whose input ``x`` is zero outside that support -- only the active halo tiles are computed, the
-    others get zeros (nothing when accumulating); bit-identical to the dense launch."""
+    others get zeros (nothing when accumulating); bit-identical to the dense launch.  An activity with ``need`` set
+    is the forward form instead: the listed tiles are the ones whose output somebody reads; they run the usual bias /
+    relu / bitmask epilogue, the others get zeros in their output rows and bitmask bytes."""
     if not hx32_covers(g):
         raise RuntimeError("conv3x3_hx32: geometry not covered")
     if not (x.is_contiguous() and w.is_contiguous() and y.is_contiguous() and x.shape[-1] == g.cin
@@ -291,7 +293,16 @@ def launch_hx32(x, w, bias, res, y, g: ConvGeom, relu: bool, accumulate: bool = 
     tiles, nt = _hx.device_tiles(_hx.geom_batch(g), _hx.geom_shapes(g), x.device)
     wp = hx32_packed(w, g.cout, g.cin)
     act = active if active is not None else _ra.current()
-    if act is not None and act.M == int(g.M) and act.ntiles == nt and bias is None and res is None and not relu:
+    fits = act is not None and act.M == int(g.M) and act.ntiles == nt
+    # the two meanings of a list stay apart: a needed-tiles activity (a forward) never reaches an accumulate or
+    # residual launch or one that READS a mask, a zero-input activity (a data gradient) never one with a bias or relu;
+    # a launch that does not fit runs dense
+    if fits and act.need and res is None and not accumulate and (mask is None or (relu and isinstance(mask, BitMask))):
+        _ra.FWD_LAUNCHES["conv"] += 1
+        return _chk(lib().mxr_conv3x3_hx32_need(_p(x), _p(wp), _p(bias), _p(mask), _p(y), _p(zero_page(x.device)),
+                                                ctypes.byref(g), _p(tiles), nt, int(relu), int(variant),
+                                                _p(act.order), _p(act.count), _s()), "conv3x3_hx32_need")
+    if fits and not act.need and bias is None and res is None and not relu:
         _ra.LAUNCHES["dgrad"] += 1
         return _chk(lib().mxr_conv3x3_hx32_act(_p(x), _p(wp), None, None, _p(mask), _p(y), _p(zero_page(x.device)),
                                                ctypes.byref(g), _p(tiles), nt, 0, int(accumulate), int(variant),

@@ -202,14 +202,22 @@ def dilate_rows(rows: np.ndarray, N: int, shapes: Sequence[Tuple[int, int]]) -> 
     return out
 
 
-def active_tiles(tab: np.ndarray, rows: np.ndarray) -> np.ndarray:
-    """bool [ntiles]: a tile is active when any of its boxes, extended by one pixel and clipped to the level, holds a
-    set row of ``rows`` (bool [P], the support of the conv's INPUT) -- exactly the tiles whose halo is not all zero."""
+def rows_positive(state: np.ndarray, group: int) -> np.ndarray:
+    """bool [M]: the packed rows that own a positive anchor.  ``state`` is the assigner's int8 [M * group]; row ``m``
+    owns anchors ``m * group .. m * group + group - 1`` (the heads reshape [B, P, 4 * group] to (B, P * group, 4))."""
+    return (np.asarray(state).reshape(-1, int(group)) == 1).any(axis=1)
+
+
+def active_tiles(tab: np.ndarray, rows: np.ndarray, ext: int = 1) -> np.ndarray:
+    """bool [ntiles]: a tile is active when any of its boxes, extended by ``ext`` pixels and clipped to the level, holds
+    a set row of ``rows`` (bool [P]).  ``ext = 1``: ``rows`` is the support of the conv's INPUT -- exactly the tiles
+    whose halo is not all zero (the sparse backward).  ``ext = 0``: ``rows`` are the OUTPUT rows somebody reads --
+    exactly the tiles that own one (the sparse forward)."""
     act = np.zeros(len(tab), dtype=bool)
     for i, row in enumerate(tab):
         for (sbeg, hoff, ib, ob, H, W, y0, x0, R, C) in _boxes(row):
-            ya, yb = max(0, y0 - 1), min(H - 1, y0 + R)
-            xa, xb = max(0, x0 - 1), min(W - 1, x0 + C)
+            ya, yb = max(0, y0 - ext), min(H - 1, y0 + R - 1 + ext)
+            xa, xb = max(0, x0 - ext), min(W - 1, x0 + C - 1 + ext)
             lv = rows[ob:ob + H * W].reshape(H, W)
             if lv[ya:yb + 1, xa:xb + 1].any():
                 act[i] = True

@@ -130,6 +130,11 @@ _SIGS = {
     "mxr_rows_nonzero": [c_vp, c_ll, c_int, c_vp, c_vp],
     "mxr_rows_dilate": [c_vp, c_vp, c_int, c_ll, ctypes.POINTER(ConvGeom), c_vp],
     "mxr_halo_active_tiles": [c_vp, c_int, c_vp, c_ll, c_int, c_vp, c_vp, c_vp],
+    # the sparse regression-tower forward (the same files)
+    "mxr_rows_positive": [c_vp, c_ll, c_int, c_vp, c_vp],
+    "mxr_halo_active_tiles_ext": [c_vp, c_int, c_vp, c_ll, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "mxr_conv3x3_hx32_need": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(ConvGeom), c_vp, c_int, c_int, c_int,
+                              c_vp, c_vp, c_vp],
     "mxr_conv_wgrad_pipe": [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp, ctypes.POINTER(ConvGeom), c_int,
                             c_vp],
     "mxr_conv_wgrad_pipe_direct": [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, ctypes.POINTER(ConvGeom), c_int, c_vp],

@@ -397,8 +397,10 @@ class PyramidConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, shapes, relu, mask_input_grad=False, grad_premasked=False, pad_sink=None,
-                join=None, out_f8=False, act=None):
+                join=None, out_f8=False, act=None, need=None):
         from .conv_tuner import TUNER
+        # need: only the listed halo tiles of this layer's output are read (row_activity.FwdChain: the regression
+        # tower under the Trainer's request); the hx32 launches walk the list, every other candidate runs dense
         # act = (row_activity.GradChain, k): this layer is k layers below the regression final, whose backward starts
         # the chain from the loss gradient's non-zero rows (bf16 heads without a norm: Submodel.forward_packed)
         ctx.act = act
@@ -458,8 +460,11 @@ class PyramidConvFn(torch.autograd.Function):
             cands = fwd_candidates(x, w, b, None, g, 1, (1, 1, 1, 1), relu, (N, P, cout), allow_miopen=False,
                                    mask=emit)
             if cout % 8 and cout < 64:
-                cands["pad64"] = lambda: _pad64_pfwd(x, w, b, shapes, relu)
-            y = TUNER.run(key, cands)
+                cands["pad64"] = lambda: _pad64_pfwd(x, w, b, shapes, relu, need=nact)
+            # (a race times and compares the dense launches)
+            nact = need if need is not None and not TUNER.needs_tuning(key, cands) else None
+            with _ra.using(nact):
+                y = TUNER.run(key, cands)
             if emit is not None:
                 y._mxr_bits = emit
         ctx.save_for_backward(x, w, y if relu else None)
@@ -497,7 +502,9 @@ class PyramidConvFn(torch.autograd.Function):
             mk = ctx.bits_in if ctx.bits_in is not None else x
         # the rows of dy that can be non-zero (ops.row_activity): the final derives them from dy itself (the mask
         # kernels run here, on the compute stream, before the side stream forks for the weight gradient), a tower
-        # layer takes the chain's dilated mask.  The final's weight gradient stays dense: its role-swapped form runs
+        # layer takes the chain's dilated mask.  (When this step's forward ran over the positive rows and its chain is
+        # still the current one of its workspace, chain.start takes that chain's masks and lists -- a superset of the
+        # gradient's rows -- and launches no mask kernel.)  The final's weight gradient stays dense: its role-swapped form runs
         # the im2col over dY (it would need the dilated mask on the K side and X on the other).
         ract = wact = None
         if ctx.act is not None and ctx.f8x is None:
@@ -583,7 +590,7 @@ class PyramidConvFn(torch.autograd.Function):
                     dw = dw.to(ctx.wdt)
                 if has_bias and ctx.needs_input_grad[2] and not fb:
                     db = deliver_bias_grad(ctx.params[1], dy, channels=cout)
-                return dx, dw, db, None, None, None, None, None, None, None, None
+                return dx, dw, db, None, None, None, None, None, None, None, None, None
             with _ra.using(wact):
                 fused_bias = (has_bias and ctx.needs_input_grad[2]
                               and deliver_wgrad_bias_fused(wkey, x, dy, gw, ctx.params[0], ctx.params[1]))
@@ -617,7 +624,7 @@ class PyramidConvFn(torch.autograd.Function):
                 dw = dw.to(ctx.wdt)
         if has_bias and ctx.needs_input_grad[2] and not fused_bias:
             db = deliver_bias_grad(ctx.params[1], dy, channels=cout)
-        return dx, dw, db, None, None, None, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None, None, None, None
 
 def _focal_fused(pad_sink, relu, b, g: ConvGeom, key: str) -> bool:
     """Whether this pyramid layer is the classification final with a focal request and a tuned conv_hx32 variant
@@ -630,17 +637,20 @@ def _focal_fused(pad_sink, relu, b, g: ConvGeom, key: str) -> bool:
             and req.A > 0 and g.cout == 80 * req.A and _cl.hx32_covers(g)
             and (TUNER.prefer(key, "hx32_10", _cl.FOCAL_PREFER_MS) or TUNER.prefer(key, "hx32_0", _cl.FOCAL_PREFER_MS)))
 
-def _pad64_pfwd(x, w, b, shapes, relu):
+def _pad64_pfwd(x, w, b, shapes, relu, need=None):
     """Narrow pyramid conv (cout < 64, e.g. the 36-output regression final) on the 64-wide kernels:
-    zero weight rows, then the first ``cout`` channels copied out (a 25 MB copy vs a 2x faster GEMM)."""
+    zero weight rows, then the first ``cout`` channels copied out (a 25 MB copy vs a 2x faster GEMM).
+    ``need``: the needed-tiles activity of the inner launch (``row_activity.FwdChain``)."""
     from .conv_tuner import TUNER
     N, P, cin = x.shape
     cout = w.shape[0]
     wp = F.pad(w, (0, 0, 0, 0, 0, 0, 0, 64 - cout)).contiguous()
     bp = None if b is None else F.pad(b, (0, 64 - cout)).contiguous()
     gp = geom_pyramid(N, shapes, cin, 64)
-    yp = TUNER.run(TUNER.key("pfwd", N, tuple(shapes), cin, 64, int(relu), "pad"),
-                   fwd_candidates(x, wp, bp, None, gp, 1, (1, 1, 1, 1), relu, (N, P, 64), allow_miopen=False))
+    key = TUNER.key("pfwd", N, tuple(shapes), cin, 64, int(relu), "pad")
+    cands = fwd_candidates(x, wp, bp, None, gp, 1, (1, 1, 1, 1), relu, (N, P, 64), allow_miopen=False)
+    with _ra.using(need if need is not None and not TUNER.needs_tuning(key, cands) else None):
+        yp = TUNER.run(key, cands)
     return yp[..., :cout].contiguous()
 
 def _pad64_pwgrad(x, dy, shapes, cout):
@@ -743,14 +753,15 @@ def pyramid_pack(xs: Sequence[torch.Tensor]):
     return packed, shapes
 
 def pyramid_conv_layer(x, shapes, layer, relu, mask_input_grad=False, grad_premasked=False,
-                       pad_sink=None, join=None, out_f8: bool = False, act=None) -> torch.Tensor:
+                       pad_sink=None, join=None, out_f8: bool = False, act=None, need=None) -> torch.Tensor:
     """``mask_input_grad``: x is a relu output whose only consumer is this layer -> its relu backward
     is fused into this layer's dgrad; ``grad_premasked``: the (sole) consumer of this layer's relu
     output does that, so skip the relu backward here; ``out_f8``: that consumer is an fp8 head layer (under fp8
     the output may then exist only as its fp8 copy and relu bitmask, ops.fp8.pyramid_forward); ``act``: the
-    (``row_activity.GradChain``, layers below the final) of a regression tower whose gradient is sparse."""
+    (``row_activity.GradChain``, layers below the final) of a regression tower whose gradient is sparse; ``need``:
+    the needed-tiles ``row_activity.Activity`` of this layer's forward (``row_activity.FwdChain.need``)."""
     return PyramidConvFn.apply(x, layer.weight, layer.bias, tuple(shapes), bool(relu), bool(mask_input_grad),
-                               bool(grad_premasked), pad_sink, join, bool(out_f8), act)
+                               bool(grad_premasked), pad_sink, join, bool(out_f8), act, need)
 
 def pyramid_unpack(y, shapes):
     out, off = [], 0

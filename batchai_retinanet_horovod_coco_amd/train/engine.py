@@ -185,6 +185,13 @@ class Trainer:
         if self.regression_bins and self._fused_losses():
             # the distribution head's integral runs on positive rows only (RetinaNet._with_integral)
             self.model.integral_request = state
+        # the losses below read the regression output on state == 1 rows only (smooth_l1_kernel / iou_loss_kernel):
+        # the model may run the regression tower's forward where that is (ops.row_activity.FwdChain).  This request is
+        # what enforces the contract: the quality losses and the distribution head read more, and get none
+        sparse_reg = (self._fused_losses() and self.classification_loss == "focal" and not self.regression_bins
+                      and self.regression_loss in ("smooth_l1", "giou", "diou", "ciou"))
+        if sparse_reg:
+            self.model.positive_request = state
         with _range("forward"):
             try:
                 out = self.model(x)
@@ -193,6 +200,8 @@ class Trainer:
                     self.model.focal_request = None
                 if self.regression_bins:
                     self.model.integral_request = None
+                if sparse_reg:
+                    self.model.positive_request = None
         with _range("backward"):
             return self._losses_backward(out, reg_t, state, label, npos, self._loss_anchors(images))
 

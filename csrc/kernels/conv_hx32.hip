@@ -122,6 +122,12 @@ __device__ __forceinline__ int h2_off(int h, int u) { return (h << 5) + ((u ^ ((
 // the count is read on the device).  An inactive tile's whole halo is zero, so its result is +0 everywhere: its
 // output slots get zeros by 16-B stores from the same launch (nothing in the accumulate form).  No bias / residual /
 // relu (the launcher checks).
+// ACT = 2, the second meaning (mxr_conv3x3_hx32_need; instantiations of its own: ACT = 1 compiles as before): a FORWARD of which only the listed tiles are needed.  The active tiles
+// run the normal forward epilogue (bias, relu, the relu output's bitmask); the inactive ones get zeros in their output
+// slots and, where the launch writes a bitmask, in their bitmask bytes -- finite and deterministic, because the next
+// layer's active tiles read their halo from them.  No residual, no accumulate (the entry point checks).
+// ACT = 3: the same without the bitmask bytes -- the generic epilogue of the variants whose bitmask-writing relu forward
+// has a compile-time form (BW), which therefore never writes a bitmask itself.
 template <int BCO, int PERS, int DIAG = 0, int HL = 0, int NWV = 8, int HB1 = 0, int WR3 = 0, int MK = 0, int FOC = 0,
           int BW = 0, int M16 = 0, int ACT = 0>
 __global__ __launch_bounds__(NWV * 64, (HB1 ? (NWV == 4 ? 3 : 4) : (NWV == 8 ? 2 : 1))) void conv3x3_hx32_kernel(
@@ -430,7 +436,9 @@ __global__ __launch_bounds__(NWV * 64, (HB1 ? (NWV == 4 ? 3 : 4) : (NWV == 8 ? 2
     // the blocks below nwork_c take the active items (remapped among themselves: the same XCD locality over a
     // dense share of every XCD), the others one inactive item each
     if constexpr (!PERS) item = (int)blockIdx.x < nwork_c ? xcd_remap(blockIdx.x, nwork_c) : (int)blockIdx.x;
-    // zeros into the output slots of an inactive tile's item: 16-B chunk ch of slot p per thread
+    // zeros into the output slots of an inactive tile's item: 16-B chunk ch of slot p per thread (ACT = 2, a relu
+    // forward that writes its output's bitmask: the chunk's bitmask byte too)
+    const bool zbits = ACT == 2 && relu && ((uintptr_t)Mk & 1);
     auto zero_item = [&](int z) {
       const HaloTile& T = tiles[tile_of(z)];
       const int zc0 = tile_co0(z);
@@ -447,8 +455,11 @@ __global__ __launch_bounds__(NWV * 64, (HB1 ? (NWV == 4 ? 3 : 4) : (NWV == 8 ? 2
           }
         const int loc = p - sb;
         const int r = fdiv(loc, C), c = loc - r * C;
-        *reinterpret_cast<uint4*>(Y + (long long)(ob + (y0 + r) * W + x0 + c) * cout + zc0 + ch * 8) =
-            make_uint4(0u, 0u, 0u, 0u);
+        const long long zoff = (long long)(ob + (y0 + r) * W + x0 + c) * cout + zc0 + ch * 8;
+        *reinterpret_cast<uint4*>(Y + zoff) = make_uint4(0u, 0u, 0u, 0u);
+        if constexpr (ACT == 2) {
+          if (zbits) mkb[zoff >> 3] = (uint8_t)0;
+        }
       }
     };
     if (!accumulate) {
@@ -861,6 +872,10 @@ namespace {
 // launch_hx32<BCO, PERS, DIAG, HL, NWV, HB1, WR3, MK, FOC, BW, M16, ACT> of hx32_dispatch's arguments
 #define HX_LAUNCH(...)                                                                                            \
   launch_hx32<__VA_ARGS__, ACT>(x, w, bias, r, mk, y, z, t, ntiles, g, relu, accumulate, stream, FocalArgs{}, al, ac)
+// the same for the variants with a BW form (0, 6, 10, 11), whose generic epilogue never writes a bitmask: ACT = 2 -> 3
+#define HX_LAUNCH_G(...)                                                                                          \
+  launch_hx32<__VA_ARGS__, (ACT == 2 ? 3 : ACT)>(x, w, bias, r, mk, y, z, t, ntiles, g, relu, accumulate, stream,    \
+                                                 FocalArgs{}, al, ac)
 
 template <int ACT>
 int hx32_dispatch(const bf16_t* x, const bf16_t* w, const float* bias, const bf16_t* r, const bf16_t* mk, bf16_t* y,
@@ -869,16 +884,20 @@ int hx32_dispatch(const bf16_t* x, const bf16_t* w, const float* bias, const bf1
   // the masked data gradient of the winning variants (0, 6) runs the compile-time masked epilogue (bf16 mask or
   // bitmask), the plain relu forward writing a bitmask its compile-time form (BW)
   const bool bits = mk != nullptr && ((uintptr_t)mk & 1);
-  const bool mk_fast = mk != nullptr && r == nullptr && !accumulate && !relu;
-  if (mk_fast && variant == 0 && !bits) return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 1, 0, 0, 0);
-  if (mk_fast && variant == 6 && !bits) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 1, 0, 0, 0);
-  if (mk_fast && variant == 0 && bits) return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 2, 0, 0, 0);
-  if (mk_fast && variant == 6 && bits) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 2, 0, 0, 0);
-  if (mk_fast && variant == 10 && !bits) return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 1, 0, 0, 1);
-  if (mk_fast && variant == 10 && bits) return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 2, 0, 0, 1);
-  if (mk_fast && variant == 11 && !bits) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 1, 0, 0, 1);
-  if (mk_fast && variant == 11 && bits) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 2, 0, 0, 1);
-  if constexpr (!ACT) {
+  if constexpr (ACT != 2) {   // (ACT = 2 is a forward: it reads no mask)
+    const bool mk_fast = mk != nullptr && r == nullptr && !accumulate && !relu;
+    if (mk_fast && variant == 0 && !bits) return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 1, 0, 0, 0);
+    if (mk_fast && variant == 6 && !bits) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 1, 0, 0, 0);
+    if (mk_fast && variant == 0 && bits) return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 2, 0, 0, 0);
+    if (mk_fast && variant == 6 && bits) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 2, 0, 0, 0);
+    if (mk_fast && variant == 10 && !bits) return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 1, 0, 0, 1);
+    if (mk_fast && variant == 10 && bits) return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 2, 0, 0, 1);
+    if (mk_fast && variant == 11 && !bits) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 1, 0, 0, 1);
+    if (mk_fast && variant == 11 && bits) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 2, 0, 0, 1);
+  }
+  // (ACT = 2: the needed-tiles forward of a tower layer; every other variant takes the generic epilogue there.
+  // ACT = 1 is a data gradient: no relu)
+  if constexpr (ACT != 1) {
     const bool bw_fast = bits && relu && r == nullptr && !accumulate;
     if (bw_fast && variant == 0) return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 0, 0, 1, 0);
     if (bw_fast && variant == 6) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 0, 0, 1, 0);
@@ -886,21 +905,21 @@ int hx32_dispatch(const bf16_t* x, const bf16_t* w, const float* bias, const bf1
     if (bw_fast && variant == 11) return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 0, 0, 1, 1);
   }
   switch (variant) {
-    case 0: return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 0, 0, 0, 0);
+    case 0: return HX_LAUNCH_G(256, 0, 0, 0, 8, 0, 0, 0, 0, 0, 0);
     case 1: return HX_LAUNCH(128, 0, 0, 0, 8, 0, 0, 0, 0, 0, 0);
     case 2: return HX_LAUNCH(256, 1, 0, 0, 8, 0, 0, 0, 0, 0, 0);
     case 3: return HX_LAUNCH(128, 1, 0, 0, 8, 0, 0, 0, 0, 0, 0);
     case 4: return HX_LAUNCH(256, 0, 0, 1, 8, 0, 0, 0, 0, 0, 0);
     case 5: return HX_LAUNCH(128, 0, 0, 1, 8, 0, 0, 0, 0, 0, 0);
-    case 6: return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 0, 0, 0, 0);
+    case 6: return HX_LAUNCH_G(128, 0, 0, 0, 8, 1, 0, 0, 0, 0, 0);
     case 7: return HX_LAUNCH(128, 0, 0, 0, 8, 0, 1, 0, 0, 0, 0);
     // 64-channel tiles for the narrow layers (the 64-padded regression final, the stage-2 64 -> 64 convs): 4 waves
     // (2 co x 2 px, 32 x 128 per wave); 9 with one halo buffer (53 KiB: three blocks share a CU)
     case 8: return HX_LAUNCH(64, 0, 0, 0, 4, 0, 0, 0, 0, 0, 0);
     case 9: return HX_LAUNCH(64, 0, 0, 0, 4, 1, 0, 0, 0, 0, 0);
     // 10 / 11 / 12: variants 0 / 6 / 1 on the 16x16x32 MFMA (M16: unswizzled plane images, one K = 32 step per tap)
-    case 10: return HX_LAUNCH(256, 0, 0, 0, 8, 0, 0, 0, 0, 0, 1);
-    case 11: return HX_LAUNCH(128, 0, 0, 0, 8, 1, 0, 0, 0, 0, 1);
+    case 10: return HX_LAUNCH_G(256, 0, 0, 0, 8, 0, 0, 0, 0, 0, 1);
+    case 11: return HX_LAUNCH_G(128, 0, 0, 0, 8, 1, 0, 0, 0, 0, 1);
     case 12: return HX_LAUNCH(128, 0, 0, 0, 8, 0, 0, 0, 0, 0, 1);
     // 13 / 14 / 15: the persistent grids 2 / 3 and the three-slot weight ring 7 on the 16x16x32 MFMA
     case 13: return HX_LAUNCH(256, 1, 0, 0, 8, 0, 0, 0, 0, 0, 1);
@@ -931,16 +950,19 @@ int hx32_dispatch(const bf16_t* x, const bf16_t* w, const float* bias, const bf1
   return -6;
 }
 #undef HX_LAUNCH
+#undef HX_LAUNCH_G
 
 }  // namespace
 
 // act_list / act_cnt (optional, both or neither): a data gradient over an input that is zero outside the support the
 // list was built from (mxr_halo_active_tiles over the same tile table): only the listed active tiles are computed,
 // the others get zeros (nothing when accumulating).  Requires no bias, residual or relu.
-MXR_API int mxr_conv3x3_hx32_act(const void* X, const void* Wt, const float* bias, const void* R, const void* Mk,
-                                 void* Y, const void* zpage, const ConvGeom* g, const void* tiles, int ntiles, int relu,
-                                 int accumulate, int variant, const int* act_list, const int* act_cnt,
-                                 hipStream_t stream) {
+// need != 0 (mxr_conv3x3_hx32_need): the list names the tiles whose output is NEEDED instead -- a forward with its
+// bias / relu / bitmask epilogue on those tiles, zeros (output and bitmask bytes) on the others.  Requires a list,
+// no residual and no accumulate.
+static int hx32_entry(const void* X, const void* Wt, const float* bias, const void* R, const void* Mk, void* Y,
+                      const void* zpage, const ConvGeom* g, const void* tiles, int ntiles, int relu, int accumulate,
+                      int variant, const int* act_list, const int* act_cnt, int need, hipStream_t stream) {
   if (g->cin % 32 != 0 || g->cout % 8 != 0) return -1;
   if (g->kh != 3 || g->kw != 3 || g->stride != 1 || g->pt != 1 || g->pl != 1 || g->ostride != 1) return -2;
   if (g->in_img != g->out_img || (g->M + 1) * (long long)std::max(g->cin, g->cout) >= (1LL << 31)) return -4;
@@ -950,12 +972,31 @@ MXR_API int mxr_conv3x3_hx32_act(const void* X, const void* Wt, const float* bia
   const HaloTile* t = (const HaloTile*)tiles;
   bf16_t* y = (bf16_t*)Y;
   if ((act_list == nullptr) != (act_cnt == nullptr)) return -7;
+  if (need && (act_list == nullptr || r != nullptr || accumulate)) return -7;
   if (act_list != nullptr) {
+    if (need)
+      return hx32_dispatch<2>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, variant, stream, act_list,
+                              act_cnt);
     if (bias != nullptr || r != nullptr || relu) return -7;
     return hx32_dispatch<1>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, variant, stream, act_list,
                             act_cnt);
   }
   return hx32_dispatch<0>(x, w, bias, r, mk, y, z, t, ntiles, *g, relu, accumulate, variant, stream, nullptr, nullptr);
+}
+
+MXR_API int mxr_conv3x3_hx32_act(const void* X, const void* Wt, const float* bias, const void* R, const void* Mk,
+                                 void* Y, const void* zpage, const ConvGeom* g, const void* tiles, int ntiles, int relu,
+                                 int accumulate, int variant, const int* act_list, const int* act_cnt,
+                                 hipStream_t stream) {
+  return hx32_entry(X, Wt, bias, R, Mk, Y, zpage, g, tiles, ntiles, relu, accumulate, variant, act_list, act_cnt, 0,
+                    stream);
+}
+
+MXR_API int mxr_conv3x3_hx32_need(const void* X, const void* Wt, const float* bias, const void* Mk, void* Y,
+                                  const void* zpage, const ConvGeom* g, const void* tiles, int ntiles, int relu,
+                                  int variant, const int* need_list, const int* need_cnt, hipStream_t stream) {
+  return hx32_entry(X, Wt, bias, nullptr, Mk, Y, zpage, g, tiles, ntiles, relu, 0, variant, need_list, need_cnt, 1,
+                    stream);
 }
 
 // variant: 0 = 256 co x 256 px (154 KiB LDS), 1 = 128 co x 256 px (105 KiB), 2 / 3 = the same on a

@@ -2,7 +2,8 @@
 //
 // The regression loss has a gradient on positive anchors only, so the gradient entering the regression final is
 // zero on all but a fraction of a percent of the packed rows, and every 3x3 data gradient below it widens that
-// support by one pixel.  These kernels derive the support FROM THE DATA (no contract with the loss or assigner):
+// support by one pixel.  The backward's kernels derive the support FROM THE DATA (no contract with the loss or
+// assigner):
 //
 // * mxr_rows_nonzero: [rows, ld] bf16 -> one bit per row (bit m % 64 of 64-bit word m / 64: word t is exactly the
 //   64-row K-tile t of conv_wgrad_p8.hip); a row is set when any element is not +-0;
@@ -11,7 +12,18 @@
 // * mxr_halo_active_tiles: per mask, the halo tiles (halo_tile.h) whose boxes, extended by one pixel and clipped
 //   to the level, hold a set bit -- as a permutation of the tile indices: the active tiles first (ascending), the
 //   inactive ones behind them, and the active count in device memory (conv_hx32.hip walks the list; the loop
-//   bounds are read on the device: no host synchronisation).
+//   bounds are read on the device: no host synchronisation).  mxr_halo_active_tiles_ext: the same with a mask
+//   index and an extension of 0 or 1 pixels per list (0: the tiles whose own OUTPUT pixels meet the mask).
+//
+// The sparse FORWARD of the regression tower starts from a contract instead: THE LOSS READS THE REGRESSION OUTPUT ON
+// state == 1 ROWS ONLY (smooth_l1_kernel / iou_loss_kernel in losses.hip), so the final's output is needed on the
+// rows M0 that own a positive anchor and the tower layer k layers below it on the k-fold dilation of M0:
+//
+// * mxr_rows_positive: the assigner's int8 anchor states -> the row mask M0 (a packed row owns `group` anchors).
+//
+// Nothing here can check that contract.  The Trainer enforces it: it hands the model the anchor states for a
+// forward only when the losses it is about to run read the regression output that way (Trainer.forward_backward's
+// request); without the request the forward is dense.
 #include "common.h"
 #include "conv_common.h"
 #include "halo_tile.h"
@@ -38,6 +50,20 @@ __global__ __launch_bounds__(256) void rows_nonzero_kernel(const uint4* __restri
   }
   __syncthreads();
   if (threadIdx.x == 0) mask[blockIdx.x] = (u64)bits[0] | ((u64)bits[1] << 32);
+}
+
+// one thread per packed row: a wave's 64 rows are one word; rows past `rows` vote clear
+__global__ __launch_bounds__(256) void rows_positive_kernel(const int8_t* __restrict__ state, long long rows, int group,
+                                                            long long nw, u64* __restrict__ mask) {
+  const long long m = (long long)blockIdx.x * 256 + threadIdx.x;
+  bool pos = false;
+  if (m < rows) {
+    const int8_t* s = state + m * group;
+    for (int a = 0; a < group; ++a) pos |= s[a] == 1;
+  }
+  const u64 bal = __ballot(pos);
+  const long long word = m >> 6;
+  if ((threadIdx.x & 63) == 0 && word < nw) mask[word] = bal;
 }
 
 // bits [s, s + len) of the mask (len <= 32, s + len <= 64 nw)
@@ -85,11 +111,12 @@ __global__ __launch_bounds__(256) void rows_dilate_kernel(const u64* __restrict_
   }
 }
 
-__device__ __forceinline__ bool ra_tile_active(const HaloTile& T, const u64* __restrict__ mask) {
+// ext: the boxes extended by that many pixels (1: the tile's halo, 0: its output pixels), clipped to the level
+__device__ __forceinline__ bool ra_tile_active(const HaloTile& T, const u64* __restrict__ mask, int ext) {
   for (int b = 0; b < T.nbox; ++b) {
     const HaloBox& B = T.b[b];
-    const int ya = max(0, B.y0 - 1), yb = min(B.H - 1, B.y0 + B.R);
-    const int xa = max(0, B.x0 - 1), xb = min(B.W - 1, B.x0 + B.C);
+    const int ya = max(0, B.y0 - ext), yb = min(B.H - 1, B.y0 + B.R - 1 + ext);
+    const int xa = max(0, B.x0 - ext), xb = min(B.W - 1, B.x0 + B.C - 1 + ext);
     for (int yy = ya; yy <= yb; ++yy) {
       long long s = (long long)B.out_base + (long long)yy * B.W + xa;
       int len = xb - xa + 1;
@@ -106,20 +133,27 @@ __device__ __forceinline__ bool ra_tile_active(const HaloTile& T, const u64* __r
   return false;
 }
 
-// one block per mask: an ordered compaction of the tile indices
+constexpr int RA_MAXLIST = 16;
+struct ListSel {   // list i: mask which[i], extension ext[i]
+  signed char which[RA_MAXLIST], ext[RA_MAXLIST];
+};
+
+// one block per list: an ordered compaction of the tile indices
 __global__ __launch_bounds__(1024) void halo_active_tiles_kernel(const HaloTile* __restrict__ tiles, int ntiles,
                                                                  const u64* __restrict__ masks, long long stride,
-                                                                 int* __restrict__ lists, int* __restrict__ counts) {
+                                                                 int* __restrict__ lists, int* __restrict__ counts,
+                                                                 ListSel sel) {
   __shared__ int wcnt[16];
   __shared__ int base_s;
-  const u64* mask = masks + (long long)blockIdx.x * stride;
+  const u64* mask = masks + (long long)sel.which[blockIdx.x] * stride;
+  const int ext = sel.ext[blockIdx.x];
   int* list = lists + (long long)blockIdx.x * ntiles;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (threadIdx.x == 0) base_s = 0;
   __syncthreads();
   for (int t0 = 0; t0 < ntiles; t0 += 1024) {
     const int t = t0 + threadIdx.x;
-    const bool act = t < ntiles && ra_tile_active(tiles[t], mask);
+    const bool act = t < ntiles && ra_tile_active(tiles[t], mask, ext);
     const u64 bal = __ballot(act);
     if (lane == 0) wcnt[wave] = __popcll(bal);
     __syncthreads();
@@ -152,6 +186,16 @@ MXR_API int mxr_rows_nonzero(const void* dy, long long rows, int ld, void* mask,
   return (int)hipGetLastError();
 }
 
+// mask: (rows + 63) / 64 words, every one written (tail bits clear).  state: int8 [rows * group], packed row m owns
+// anchors m * group .. m * group + group - 1; a row is set when one of them has state == 1.
+MXR_API int mxr_rows_positive(const void* state, long long rows, int group, void* mask, hipStream_t stream) {
+  if (rows < 1 || group < 1) return -1;
+  const long long nw = (rows + 63) / 64;
+  if (nw > 0x7fffffffLL) return -4;
+  rows_positive_kernel<<<(unsigned)((nw + 3) / 4), 256, 0, stream>>>((const int8_t*)state, rows, group, nw, (u64*)mask);
+  return (int)hipGetLastError();
+}
+
 // out + (k - 1) * stride_words: the k-fold 3x3 dilation of `in` per image and level of g (k = 1 .. nd <= 8); masks of
 // (g->M + 63) / 64 words over the packed output rows of g.
 MXR_API int mxr_rows_dilate(const void* in, void* out, int nd, long long stride_words, const ConvGeom* g,
@@ -167,10 +211,30 @@ MXR_API int mxr_rows_dilate(const void* in, void* out, int nd, long long stride_
 
 // For each of the nmask row masks (masks + k * stride_words): lists + k * ntiles = the tile indices, the active
 // ones first; counts[k] = how many are active.
+// List i (lists + i * ntiles, counts[i]) is built from mask which[i] (0 .. nmask - 1) with the boxes extended by ext[i]
+// (0 or 1) pixels; which / ext are HOST arrays of nlist <= 16 entries.
+MXR_API int mxr_halo_active_tiles_ext(const void* tiles, int ntiles, const void* masks, long long stride_words,
+                                      int nmask, int nlist, const int* which, const int* ext, int* lists, int* counts,
+                                      hipStream_t stream) {
+  if (ntiles < 1 || nmask < 1 || nlist < 1 || nlist > RA_MAXLIST) return -1;
+  ListSel sel = {};
+  for (int i = 0; i < nlist; ++i) {
+    if (which[i] < 0 || which[i] >= nmask || (ext[i] != 0 && ext[i] != 1)) return -1;
+    sel.which[i] = (signed char)which[i];
+    sel.ext[i] = (signed char)ext[i];
+  }
+  halo_active_tiles_kernel<<<(unsigned)nlist, 1024, 0, stream>>>((const HaloTile*)tiles, ntiles, (const u64*)masks,
+                                                                 stride_words, lists, counts, sel);
+  return (int)hipGetLastError();
+}
+
 MXR_API int mxr_halo_active_tiles(const void* tiles, int ntiles, const void* masks, long long stride_words, int nmask,
                                   int* lists, int* counts, hipStream_t stream) {
-  if (ntiles < 1 || nmask < 1) return -1;
-  halo_active_tiles_kernel<<<(unsigned)nmask, 1024, 0, stream>>>((const HaloTile*)tiles, ntiles, (const u64*)masks,
-                                                                 stride_words, lists, counts);
-  return (int)hipGetLastError();
+  if (nmask < 1 || nmask > RA_MAXLIST) return -1;
+  int which[RA_MAXLIST], ext[RA_MAXLIST];
+  for (int i = 0; i < nmask; ++i) {
+    which[i] = i;
+    ext[i] = 1;
+  }
+  return mxr_halo_active_tiles_ext(tiles, ntiles, masks, stride_words, nmask, nmask, which, ext, lists, counts, stream);
 }
