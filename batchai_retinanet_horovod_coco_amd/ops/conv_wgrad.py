@@ -1,6 +1,13 @@
 """Weight and bias gradients of the convolutions: split-K implicit GEMMs with slab
 reductions, the halo-staged 3x3 form, the 64-channel 3x3 kernel, column-sum bias gradients, and their
 delivery into the flat gradient buffer (gradient sinks, side stream) -- split out of ``native_conv``.
+
+One builder, :func:`wgrad_candidates`, offers every weight-gradient form of a geometry (:data:`_KINDS`, the library
+form, the caller's extras) as fresh-tensor or accumulate-into-slot candidates, whole or one name at a time.  One
+function, :func:`_deliver`, runs a launch into gradient slots and notifies the parameters, on the side stream or the
+current one; the entries (:func:`deliver_wgrad`, :func:`deliver_wgrad_bias_fused`, :func:`run_wgrad_proj`,
+:func:`deliver_bias_grad`, ``fp8.deliver_pyramid_wgrad``) only say which slots, which reads, which stream and what
+to launch.
 """
 from __future__ import annotations
 
@@ -13,7 +20,7 @@ import torch.nn.functional as F
 
 from . import native as _n
 from .native import ConvGeom, _chk, _p, _s, lib, zero_page, c_int, c_ll, c_vp
-from .side_stream import SIDE
+from .side_stream import SIDE, _NULL
 from . import row_activity as _ra
 from .conv_launch import (_bind, _miopen_wgrad, _only, geom_single)
 
@@ -152,40 +159,58 @@ def conv_wgrad(x, dy, g: ConvGeom, scale: Optional[torch.Tensor], out: Optional[
                                 _p(zero_page(dy.device)), ctypes.byref(g), variant, _s()), "conv_wgrad")
     return out
 
-def wgrad_candidates(x, dy, g, scale, only: Optional[str] = None):
-    if only is not None:
-        return _only_wgrad(only, x, dy, g, scale, None)
-    vs = _wgrad_variants(g)
-    c = {"hip%d" % v: (lambda v=v: conv_wgrad(x, dy, g, scale, variant=v)) for v in vs}
-    if w64_covers(g):
-        c["w64"] = lambda: wgrad3x3_c64(x, dy, scale)
-    if whalo_covers(g):
-        c["whalo"] = lambda: halo_wgrad(x, dy, g, scale)
+def _hip_names(g: ConvGeom, only):
+    if only is None:
+        return ["hip%d" % v for v in _wgrad_variants(g)]
+    return [only] if only[:3] == "hip" and only[3:].isdigit() and int(only[3:]) in _wgrad_variants(g) else []
+
+def _one_name(name: str, covers):
+    return lambda g, only: [name] if (only is None or only == name) and covers(g) else []
+
+# The native kinds of weight-gradient candidate, in race order.  Per kind: the names offered for a geometry (all of
+# them, or just ``only``), the launcher of a name into ``out`` (None: a fresh tensor), and the shape the kernel takes
+# the parameter's gradient slot in (None: as it is).  Launchers are looked up when they run (tests replace them).
+_KINDS = (
+    (_hip_names,
+     lambda n, x, dy, g, scale, out, acc: conv_wgrad(x, dy, g, scale, out=out, accumulate=acc, variant=int(n[3:])),
+     None),
+    (_one_name("w64", lambda g: w64_covers(g)),
+     lambda n, x, dy, g, scale, out, acc: wgrad3x3_c64(x, dy, scale, out=out, accumulate=acc),
+     lambda g: (64, 3, 3, 64)),
+    (_one_name("whalo", lambda g: whalo_covers(g)),
+     lambda n, x, dy, g, scale, out, acc: halo_wgrad(x, dy, g, scale, out=out, accumulate=acc),
+     lambda g: (g.cout, 3, 3, g.cin)),
+)
+_LIB = "miopen"
+_ORDER = {False: _KINDS + (_LIB,), True: _KINDS[:1] + (_LIB,) + _KINDS[1:]}      # by "accumulating"
+
+def wgrad_candidates(x, dy, g, scale, only: Optional[str] = None, sink: Optional[torch.Tensor] = None, lib_fn=None,
+                     extra=None):
+    """{name: launch} of the weight gradient of ``g``, in race order: the native kinds (:data:`_KINDS`), the library
+    form ``miopen`` when ``lib_fn`` is given, then the caller's ``extra`` ``{name: fn}``.  Without ``sink`` every
+    candidate returns a fresh fp32 gradient; with it every candidate accumulates into ``sink`` (a parameter's slot,
+    or a scratch copy of it) -- the native kinds through their kernels' accumulate form, ``lib_fn`` and ``extra``
+    (which return a fresh tensor) by adding their result.  ``only``: build that one candidate and nothing else
+    ({} when it is not offered here); the tuned dispatch's fast path (``conv_launch._only``).
+    The two forms differ in where ``miopen`` sits (after the native kinds / right after the ``hipN`` names): the
+    recorded race orders (tests/fixtures/wgrad_candidates.json), which decide ties and untuned captures."""
+    acc = sink is not None
+    c = {}
+
+    def fresh(name, fn):
+        if fn is not None and (only is None or only == name):
+            c[name] = (lambda: sink.add_(fn())) if acc else fn
+    for kind in _ORDER[acc]:
+        if kind is _LIB:
+            fresh(_LIB, lib_fn)
+            continue
+        names, launch, view = kind
+        for name in names(g, only):
+            out = sink.view(view(g)) if acc and view is not None else sink
+            c[name] = lambda name=name, launch=launch, out=out: launch(name, x, dy, g, scale, out, acc)
+    for name, fn in (extra or {}).items():
+        fresh(name, fn)
     return c
-
-_WGRAD_VS = None
-
-def _only_wgrad(only, x, dy, g, scale, sink):
-    """The one wgrad candidate ``only`` (plain, or accumulating into ``sink``); {} if not a candidate here
-    (the library form is added by the callers)."""
-    global _WGRAD_VS
-    if _WGRAD_VS is None:
-        _WGRAD_VS = set(list(_WGRAD_TILE) + list(_WGRAD_PIPE_TILE) + list(_WGRAD_P8))
-    if only.startswith("hip") and (int(only[3:]) in _WGRAD_VS or
-                                   (int(only[3:]) in _WGRAD_DIRECT and direct_covers(g))):
-        v = int(only[3:])
-        if sink is None:
-            return {only: lambda: conv_wgrad(x, dy, g, scale, variant=v)}
-        return {only: lambda: conv_wgrad(x, dy, g, scale, out=sink, accumulate=True, variant=v)}
-    if only == "w64" and w64_covers(g):
-        if sink is None:
-            return {only: lambda: wgrad3x3_c64(x, dy, scale)}
-        return {only: lambda: wgrad3x3_c64(x, dy, scale, out=sink.view(64, 3, 3, 64), accumulate=True)}
-    if only == "whalo" and whalo_covers(g):
-        if sink is None:
-            return {only: lambda: halo_wgrad(x, dy, g, scale)}
-        return {only: lambda: halo_wgrad(x, dy, g, scale, out=sink.view(g.cout, 3, 3, g.cin), accumulate=True)}
-    return {}
 
 def whalo_covers(g: ConvGeom) -> bool:
     """3x3 / stride 1 / pad 1 with Cin % 64 == 0 and Cout >= 64 (single level or packed pyramid):
@@ -303,55 +328,61 @@ def _sink(param):
     gs = _n.grad_sinks()
     return gs.get(param) if gs is not None else None
 
-def deliver_bias_grad(param, dy, scale=None, channels: Optional[int] = None):
-    """Bias gradient for ``param``: straight into its flat-gradient slot when a sink is active
-    (returns None so autograd does not add it again), else a tensor."""
-    sink = _sink(param)
-    if sink is None:
-        return bias_grad(dy, scale, channels=channels)
-    if SIDE.usable(dy):
-        with SIDE.run(dy.device, dy, scale):
-            bias_grad(dy, scale, out=sink, accumulate=True, channels=channels)
-            _n.grad_sinks().notify(param)
-        return None
-    bias_grad(dy, scale, out=sink, accumulate=True, channels=channels)
-    _n.grad_sinks().notify(param)
-    return None
-
-
-
 def _side(sink, param) -> bool:
     """Whether this weight gradient goes to the side stream: not for parameters tagged ``mxr_main_wgrad``
     (models.resnet: the last blocks of the backward, whose weight gradients would otherwise queue at the
     end of the side stream's backlog while the compute stream idles before the optimizer)."""
     return SIDE.usable(sink) and not getattr(param, "mxr_main_wgrad", False)
 
-def _deliver_wgrad(key, cands, sink_cands, param, reads=()):
-    """Run the tuned wgrad; with a gradient sink for ``param`` accumulate into it and return None.
-    Once the sink form is tuned it runs on the side stream (``ops.side_stream``), overlapped with the
-    data gradients; ``reads`` = the compute-stream tensors it reads (x, dY, scale)."""
+def _deliver(params, side: bool, device, reads, fn) -> None:
+    """The one delivery path of every gradient that accumulates into its parameter's slot: run ``fn`` (the launch
+    into the slots of ``params``), then notify each parameter in order -- inside a side-stream region when ``side``
+    (``ops.side_stream``: ``reads`` = the compute-stream tensors ``fn`` reads, and the notify inside the region so a
+    bucket-ready event covers both streams), else on the current stream."""
+    with SIDE.run(device, *reads) if side else _NULL:
+        fn()
+        gs = _n.grad_sinks()
+        for p in params:
+            gs.notify(p)
+
+def _tuned(key, make, *slots):
+    """(the accumulating candidates ``make(*slots)``, whether they were raced): a set the tuner would time is first
+    raced on scratch copies of the slots; the caller then runs the winner for real -- serially, like every first
+    sight of a shape."""
+    from .conv_tuner import TUNER
+    c = make(*slots)
+    if not TUNER.needs_tuning(key, c):
+        return c, False
+    TUNER.run(key, make(*[s.clone() for s in slots]))
+    return c, True
+
+def deliver_bias_grad(param, dy, scale=None, channels: Optional[int] = None):
+    """Bias gradient for ``param``: straight into its flat-gradient slot when a sink is active
+    (returns None so autograd does not add it again), else a tensor."""
+    sink = _sink(param)
+    if sink is None:
+        return bias_grad(dy, scale, channels=channels)
+    _deliver((param,), SIDE.usable(dy), dy.device, (dy, scale),
+             lambda: bias_grad(dy, scale, out=sink, accumulate=True, channels=channels))
+    return None
+
+def deliver_wgrad(key, x, dy, g: ConvGeom, scale, param, reads, lib_fn, extra=None):
+    """Run the tuned wgrad of ``g`` (:func:`wgrad_candidates` with ``lib_fn`` / ``extra``); with a gradient sink for
+    ``param`` accumulate into it and return None.  Once the sink form is tuned it runs on the side stream
+    (``ops.side_stream``), overlapped with the data gradients; ``reads`` = the compute-stream tensors it reads."""
     from .conv_tuner import TUNER
     sink = _sink(param)
     if sink is None:
-        return TUNER.run(key, cands() if callable(cands) else cands)
+        return TUNER.run(key, wgrad_candidates(x, dy, g, scale, lib_fn=lib_fn, extra=extra))
     key = key + "|s"        # accumulate-into-sink forms: the library path pays an extra add
+
+    def make(slot, only=None):
+        return wgrad_candidates(x, dy, g, scale, only=only, sink=slot, lib_fn=lib_fn, extra=extra)
     only = _only(key)
-    c = sink_cands(sink, only) if only is not None else None
+    c, raced = (make(sink, only) if only is not None else None), False
     if not c:
-        c = sink_cands(sink)
-        if TUNER.needs_tuning(key, c):
-            TUNER.run(key, sink_cands(sink.clone()))    # time against a scratch copy of the slot
-            c = sink_cands(sink)
-            TUNER.run(key, c)
-            _n.grad_sinks().notify(param)
-            return None
-    if _side(sink, param):
-        with SIDE.run(sink.device, *reads):
-            TUNER.run(key, c)
-            _n.grad_sinks().notify(param)
-        return None
-    TUNER.run(key, c)
-    _n.grad_sinks().notify(param)
+        c, raced = _tuned(key, make, sink)
+    _deliver((param,), not raced and _side(sink, param), sink.device, reads, lambda: TUNER.run(key, c))
     return None
 
 def _is_p8(name: str) -> bool:
@@ -381,39 +412,13 @@ def deliver_wgrad_bias_fused(key, x, dy, g: ConvGeom, wparam, bparam) -> bool:
         p8 = sorted((v, n) for n, v in t.items() if isinstance(v, float) and _is_p8(n))
         if p8 and TUNER.prefer(key, p8[0][1], dy.numel() * dy.element_size() / 4.0e9):
             win = p8[0][1]
-    if win is not None and _is_p8(win):
-        v = int(win[3:])
-
-        def run():
-            conv_wgrad(x, dy, g, None, out=ws, accumulate=True, variant=v, bias_out=bs, bias_accumulate=True)
-            gs.notify(wparam)
-            gs.notify(bparam)
-    else:
+    if win is None or not _is_p8(win):
         return False
+    v = int(win[3:])
     TUNER.calls[key] = TUNER.calls.get(key, 0) + 1
-
-    if _side(ws, wparam):
-        with SIDE.run(ws.device, x, dy):
-            run()
-    else:
-        run()
+    _deliver((wparam, bparam), _side(ws, wparam), ws.device, (x, dy),
+             lambda: conv_wgrad(x, dy, g, None, out=ws, accumulate=True, variant=v, bias_out=bs, bias_accumulate=True))
     return True
-
-def _wgrad_sink_cands(x, dy, g, scale, lib_fn):
-    def make(sink, only=None):
-        if only is not None:
-            if only == "miopen":
-                return {only: lambda: sink.add_(lib_fn())}
-            return _only_wgrad(only, x, dy, g, scale, sink)
-        vs = _wgrad_variants(g)
-        c = {"hip%d" % v: (lambda v=v: conv_wgrad(x, dy, g, scale, out=sink, accumulate=True, variant=v)) for v in vs}
-        c["miopen"] = lambda: sink.add_(lib_fn())
-        if w64_covers(g):
-            c["w64"] = lambda: wgrad3x3_c64(x, dy, scale, out=sink.view(64, 3, 3, 64), accumulate=True)
-        if whalo_covers(g):
-            c["whalo"] = lambda: halo_wgrad(x, dy, g, scale, out=sink.view(g.cout, 3, 3, g.cin), accumulate=True)
-        return c
-    return make
 
 def run_wgrad(x, dy, w, stride, pads, scale, param=None) -> Optional[torch.Tensor]:
     """Tuned fp32 weight gradient (OHWI), scaled by the folded frozen-BN scale.  With an active
@@ -423,14 +428,9 @@ def run_wgrad(x, dy, w, stride, pads, scale, param=None) -> Optional[torch.Tenso
     cout, kh = w.shape[0], w.shape[1]
     Ho, Wo = dy.shape[1], dy.shape[2]
     g = geom_single(N, H, W, Ho, Wo, kh, stride, pads, cin, cout)
-    lib_fn = lambda: _miopen_wgrad(x, w, dy, stride, pads, scale)   # noqa: E731
-
-    def cands():        # built only without a gradient sink (the training step always has one)
-        c = wgrad_candidates(x, dy, g, scale)
-        c["miopen"] = lib_fn
-        return c
     key = TUNER.key("wgrad", N, H, W, cin, cout, kh, stride, tuple(pads))
-    return _deliver_wgrad(key, cands, _wgrad_sink_cands(x, dy, g, scale, lib_fn), param, (x, dy, scale))
+    return deliver_wgrad(key, x, dy, g, scale, param, (x, dy, scale),
+                         lambda: _miopen_wgrad(x, w, dy, stride, pads, scale))
 
 def run_wgrad_bias_fused(x, dy, w, stride, pads, scale, param, bias_param) -> bool:
     """:func:`deliver_wgrad_bias_fused` for a single-geometry conv (the FPN convs: biased, unscaled);
@@ -501,26 +501,10 @@ def run_wgrad_proj(h2, x, dy, stride, s2c, s1, p2c, p1) -> bool:
     key = TUNER.key("wgradp", N, Ho, Wo, k1, cin, cout, stride, H, W) + "|s"
     win = TUNER.winner(key)
     if win is not None and win.startswith("p8d_") and int(win[4:]) in _WGRAD_DUAL:
-        c = {win: cand(int(win[4:]), o1, o2)}
+        c, raced = {win: cand(int(win[4:]), o1, o2)}, False
     else:
-        c = {"p8d_%d" % v: cand(v, o1, o2) for v in _WGRAD_DUAL}
-        if TUNER.needs_tuning(key, c):
-            # race on scratch copies of the two slots, then run the winner for real (serially, like a first sight)
-            a1, a2 = o1.clone(), o2.clone()
-            TUNER.run(key, {"p8d_%d" % v: cand(v, a1, a2) for v in _WGRAD_DUAL})
-            TUNER.run(key, c)
-            gs.notify(p2c)
-            gs.notify(p1)
-            return True
-    if _side(o1, p2c):
-        with SIDE.run(o1.device, h2, x, dy, sc1, sc2):
-            TUNER.run(key, c)
-            gs.notify(p2c)
-            gs.notify(p1)
-        return True
-    TUNER.run(key, c)
-    gs.notify(p2c)
-    gs.notify(p1)
+        c, raced = _tuned(key, lambda d1, d2: {"p8d_%d" % v: cand(v, d1, d2) for v in _WGRAD_DUAL}, o1, o2)
+    _deliver((p2c, p1), not raced and _side(o1, p2c), o1.device, (h2, x, dy, sc1, sc2), lambda: TUNER.run(key, c))
     return True
 
 

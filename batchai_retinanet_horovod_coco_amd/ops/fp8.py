@@ -577,29 +577,18 @@ def deliver_pyramid_wgrad(f8x, f8dy, g: ConvGeom, param, reads=(), bias_param=No
     usable, like the bf16 wgrads; returns None), or as a tensor when the parameter has no sink.  ``bias_param``
     (with a sink, :data:`WGRAD_BIAS`): its gradient comes out of the same kernel; callers check
     :func:`bias_fusable` first."""
-    from . import native as _n
-    from .side_stream import SIDE
+    from .conv_wgrad import _deliver, _side, _sink
     xq, ix = f8x
     dq, idq = f8dy
-    gs = _n.grad_sinks()
-    sink = gs.get(param) if gs is not None else None
+    sink = _sink(param)
     if sink is None:
         return pyramid_wgrad(xq, ix, dq, idq, g)
     out = sink.view(g.cout, g.kh, g.kw, g.cin)
-    bsink = gs.get(bias_param) if bias_param is not None else None
-
-    def run():
-        pyramid_wgrad(xq, ix, dq, idq, g, out=out, accumulate=True, variant=WGRAD_VARIANT, bias_out=bsink,
-                      bias_accumulate=True)
-        gs.notify(param)
-        if bsink is not None:
-            gs.notify(bias_param)
-    side = SIDE.usable(sink) and not getattr(param, "mxr_main_wgrad", False)
-    if side:
-        with SIDE.run(sink.device, xq, ix, dq, idq, *reads):
-            run()
-        return None
-    run()
+    bsink = _sink(bias_param) if bias_param is not None else None
+    _deliver((param,) if bsink is None else (param, bias_param), _side(sink, param), sink.device,
+             (xq, ix, dq, idq) + tuple(reads),
+             lambda: pyramid_wgrad(xq, ix, dq, idq, g, out=out, accumulate=True, variant=WGRAD_VARIANT, bias_out=bsink,
+                                   bias_accumulate=True))
     return None
 
 

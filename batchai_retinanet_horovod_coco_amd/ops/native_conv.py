@@ -35,10 +35,10 @@ from .conv_dgrad import (  # noqa: F401  (re-exported: the public surface of nat
     proj_dgrad_fusable, run_dgrad_proj, _dgrad_cands, _dgrad_s2_subpixel, _pick_taps, _s2_phase_taps, _s2_stack_taps,
     _s2_stacked_weights, _s2_stacked_weights_hip, conv_dgrad, run_dgrad,)
 from .conv_wgrad import (  # noqa: F401  (re-exported: the public surface of native_conv)
-    proj_wgrad_fusable, run_wgrad_proj, _WGRAD_P8, _WGRAD_PIPE_OCC, _WGRAD_PIPE_TILE, _WGRAD_TILE, _WGRAD_VS, _WH_TILES, _deliver_wgrad,
-    _only_wgrad, _sink, _splits, _splits_pipe, _wgrad_sink_cands, _wh_box, bias_grad, conv_wgrad,
-    deliver_bias_grad, deliver_wgrad_bias_fused, halo_wgrad, halo_wgrad_tiles, run_wgrad, run_wgrad_bias_fused,
-    w64_covers, wgrad3x3_c64, wgrad_candidates, whalo_covers,)
+    proj_wgrad_fusable, run_wgrad_proj, _WGRAD_P8, _WGRAD_PIPE_OCC, _WGRAD_PIPE_TILE, _WGRAD_TILE, _WH_TILES, _sink,
+    _splits, _splits_pipe, _wh_box, bias_grad, conv_wgrad, deliver_bias_grad, deliver_wgrad, deliver_wgrad_bias_fused,
+    halo_wgrad, halo_wgrad_tiles, run_wgrad, run_wgrad_bias_fused, w64_covers, wgrad3x3_c64, wgrad_candidates,
+    whalo_covers,)
 
 
 class GradJoin:
@@ -597,29 +597,10 @@ class PyramidConvFn(torch.autograd.Function):
         if f8_only_in and ctx.needs_input_grad[1]:
             raise RuntimeError("PyramidConvFn: a bf16 weight gradient over an fp8-only tower output")
         if ctx.needs_input_grad[1] and not fused_bias:
-            cands = wgrad_candidates(x, dy, gw, None)
-            dyl = dy if dy.shape[-1] == cout else dy[..., :cout]
-            lib_fn = lambda: _miopen_pyramid_wgrad(x, w, dyl, shapes)   # noqa: E731
-            cands["miopen"] = lib_fn
-            sink_make = _wgrad_sink_cands(x, dy, gw, None, lib_fn)
-            if cout % 8 and cout < 64:
-                # narrow regression final (36): the 64-wide pipelined wgrad on zero-padded dY rows
-                # or the role-swapped GEMM (im2col over dY, X as the wide operand)
-                narrow = {"pad64": lambda: _pad64_pwgrad(x, dy, shapes, cout)}
-                if SWAP_NARROW_WGRAD:
-                    narrow["swap"] = lambda: _swap_pwgrad(x, dy, shapes, cout)
-                cands.update(narrow)
-                base_make = sink_make
-
-                def sink_make(sink, only=None, base_make=base_make, narrow=narrow):
-                    if only in narrow:
-                        return {only: lambda: sink.add_(narrow[only]())}
-                    c = base_make(sink, only)
-                    if only is None:
-                        c.update({n: (lambda fn=fn: sink.add_(fn())) for n, fn in narrow.items()})
-                    return c
+            lib_fn = lambda: _miopen_pyramid_wgrad(x, w, dy if dy.shape[-1] == cout else dy[..., :cout], shapes)  # noqa: E731
             with _ra.using(wact):
-                dw = _deliver_wgrad(wkey, cands, sink_make, ctx.params[0], (x, dy))
+                dw = deliver_wgrad(wkey, x, dy, gw, None, ctx.params[0], (x, dy), lib_fn,
+                                   extra=_narrow_wgrads(x, dy, shapes, cout))
             if dw is not None:
                 dw = dw.to(ctx.wdt)
         if has_bias and ctx.needs_input_grad[2] and not fused_bias:
@@ -652,6 +633,17 @@ def _pad64_pfwd(x, w, b, shapes, relu, need=None):
     with _ra.using(need if need is not None and not TUNER.needs_tuning(key, cands) else None):
         yp = TUNER.run(key, cands)
     return yp[..., :cout].contiguous()
+
+def _narrow_wgrads(x, dy, shapes, cout):
+    """The extra weight-gradient forms of a narrow pyramid final (36 regression outputs; None for the other layers):
+    the 64-wide pipelined wgrad on zero-padded dY rows, or the role-swapped GEMM (im2col over dY, X as the wide
+    operand)."""
+    if not (cout % 8 and cout < 64):
+        return None
+    narrow = {"pad64": lambda: _pad64_pwgrad(x, dy, shapes, cout)}
+    if SWAP_NARROW_WGRAD:
+        narrow["swap"] = lambda: _swap_pwgrad(x, dy, shapes, cout)
+    return narrow
 
 def _pad64_pwgrad(x, dy, shapes, cout):
     """fp32 (cout, 3, 3, cin) weight gradient of a narrow pyramid conv through the 64-wide kernels."""

@@ -55,7 +55,8 @@ def test_wgrad_only_matches_full(shape):
     x, w, dy, g, _ = _tensors(*shape)
     full = NC.wgrad_candidates(x, dy, g, None)
     sink = torch.zeros(w.numel(), dtype=torch.float32)
-    make = NC._wgrad_sink_cands(x, dy, g, None, lambda: None)
+    def make(sink, only=None):
+        return NC.wgrad_candidates(x, dy, g, None, only=only, sink=sink, lib_fn=lambda: None)
     full_s = make(sink)
     assert set(full) | {"miopen"} == set(full_s)
     for name in full:

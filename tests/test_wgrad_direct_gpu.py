@@ -102,7 +102,8 @@ def test_direct_candidates_join_the_race_only_where_covered(cuda):
     names = set(CW.wgrad_candidates(x, dy, g, scale))
     assert {"hip30", "hip31"} <= names
     sink = torch.zeros(g.cout * 9 * g.cin, device=cuda)
-    make = CW._wgrad_sink_cands(x, dy, g, scale, lambda: None)
+    def make(sink, only=None):
+        return CW.wgrad_candidates(x, dy, g, scale, only=only, sink=sink, lib_fn=lambda: None)
     assert {"hip30", "hip31"} <= set(make(sink))
     assert list(make(sink, "hip30")) == ["hip30"]
     for other in ("short_ring", "pyramid"):        # too few tiles / a packed pyramid: not raced

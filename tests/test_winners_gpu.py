@@ -164,11 +164,11 @@ def _single(key, winner, dev, gen):
             # the gradient slot is a view of the flat buffer shaped like the OHWI parameter
             base = torch.randn(cout, kh, kh, cin, generator=gen, device=dev) * float(ref.abs().max())
             sink = base.clone()
-            c = NC._wgrad_sink_cands(x, dy, g, scale, lib_fn)(sink, only=winner)
+            c = NC.wgrad_candidates(x, dy, g, scale, only=winner, sink=sink, lib_fn=lib_fn)
             assert winner in c, "winner %s is not a candidate of %s" % (winner, key)
             c[winner]()
             return _err(sink - base, ref)
-        c = NC.wgrad_candidates(x, dy, g, scale, only=winner) if winner != "miopen" else {winner: lib_fn}
+        c = NC.wgrad_candidates(x, dy, g, scale, only=winner, lib_fn=lib_fn)
         assert winner in c, "winner %s is not a candidate of %s" % (winner, key)
         return _err(c[winner](), ref)
     raise AssertionError("unknown key kind " + kind)
@@ -231,7 +231,7 @@ def _pyramid(key, winner, dev, gen):
         sink = None
         if "s" in flags:
             sink = torch.zeros(cw, 3, 3, cin, device=dev)
-        c = NC._only_wgrad(winner, x, dy, gw, None, sink)
+        c = NC.wgrad_candidates(x, dy, gw, None, only=winner, sink=sink)
         assert winner in c, "winner %s is not a candidate of %s" % (winner, key)
         got = c[winner]()
         return _err(sink if sink is not None else got, ref)
