@@ -14,7 +14,8 @@ Here the host work moves into worker PROCESSES:
   arithmetic as ``data/device_preprocess.py``, so annotations are bit-identical to the thread path) and
   writes the uint8 pixels into a slot of one shared-memory arena (``multiprocessing.shared_memory``), which
   the parent registers with the HIP runtime once (``hipHostRegister``: the host->device copy reads the
-  arena directly, no staging copy);
+  arena directly, no staging copy; where the platform cannot register host memory, e.g. a virtualised GPU,
+  each copy goes through a pinned staging tensor instead);
 * a collector thread in the parent turns each finished slot into the padded device batch on a copy stream (one
   copy of the slot's used range and one launch of the warp / normalise / resize / pad kernel of
   ``csrc/kernels/image.hip``; ``device_preprocess.TRAIN_FUSED = False``: a copy and two kernels per image), waits
@@ -224,8 +225,12 @@ class ProcessEnqueuer:
         self.arena = torch.frombuffer(self.shm.buf, dtype=torch.uint8).view(self.nslots, self.slot_bytes)
         self._registered = False
         if self.device.type == "cuda":
-            try:        # pin the arena: the H2D copies read it directly
-                rc = torch.cuda.cudart().cudaHostRegister(self.arena.data_ptr(), self.arena.numel(), 0)
+            # pin the arena: the H2D copies read it directly.  Where the platform cannot register host memory
+            # (mxr_host_register leaves no pending HIP error behind) each copy goes through a pinned staging tensor
+            try:
+                from ..ops import native
+                torch.cuda.init()
+                rc = native.lib().mxr_host_register(self.arena.data_ptr(), self.arena.numel())
                 self._registered = int(rc) == 0
             except Exception:  # noqa: BLE001
                 self._registered = False
@@ -280,7 +285,8 @@ class ProcessEnqueuer:
         if self._registered:
             try:
                 torch.cuda.synchronize(self.device)
-                torch.cuda.cudart().cudaHostUnregister(self.arena.data_ptr())
+                from ..ops import native
+                native.lib().mxr_host_unregister(self.arena.data_ptr())
             except Exception:  # noqa: BLE001
                 pass
             self._registered = False

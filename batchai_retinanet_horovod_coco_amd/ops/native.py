@@ -175,6 +175,8 @@ _SIGS = {
     "mxr_s2_stack": [c_vp, c_vp, c_int, c_int, c_vp, c_vp],
     "mxr_pyr_pack": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp],
     "mxr_pyr_pack_f8": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_float, c_vp],
+    "mxr_host_register": [c_vp, c_ll],
+    "mxr_host_unregister": [c_vp],
 }
 _OPTIONAL = {"mxr_conv_wgrad", "mxr_bias_grad", "mxr_relu_bwd"}
 

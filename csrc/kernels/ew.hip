@@ -351,3 +351,21 @@ MXR_API void* mxr_stream_create_cumask(int num, int den, int priority) {
   (void)priority;
   return s;
 }
+
+// Page-lock `bytes` of host memory the caller already owns (the process loader's shared-memory arena: the workers
+// attach to it by name, so it cannot come from hipHostMalloc) so that host->device copies read it directly.
+// Returns the HIP error code.  Where the platform cannot register host memory (virtualised GPUs answer
+// hipErrorInvalidValue) the error is taken out of the runtime's per-thread last-error slot before returning:
+// left there, the next kernel launch's error check on this thread reports it as its own.
+MXR_API int mxr_host_register(void* p, long long bytes) {
+  if (!p || bytes <= 0) return (int)hipErrorInvalidValue;
+  const hipError_t rc = hipHostRegister(p, (size_t)bytes, hipHostRegisterDefault);
+  if (rc != hipSuccess) (void)hipGetLastError();
+  return (int)rc;
+}
+
+MXR_API int mxr_host_unregister(void* p) {
+  const hipError_t rc = hipHostUnregister(p);
+  if (rc != hipSuccess) (void)hipGetLastError();
+  return (int)rc;
+}
