@@ -10,7 +10,8 @@ Same subcommands, flags, defaults and argument checks as ``/root/reference/train
 ``--bucket-mb``, ``--allreduce-dtype``, ``--workers``, ``--shard-data``, ``--checkpoint-format``,
 ``--lr``, ``--clipnorm``, ``--optimizer``, ``--momentum``, ``--nesterov``, ``--weight-decay``, ``--ema-decay``, ``--weights-ema``, ``--regression-loss``, ``--regression-weight``, ``--classification-loss``, ``--head-norm``, ``--head-norm-groups``, ``--regression-bins``, ``--regression-range``, ``--dfl-weight``, ``--warmup-epochs``, ``--seed``, ``--log-every``, ``--no-metric-average``, ``--log-all-ranks``,
 ``--metrics-jsonl``, ``--stop-on-nan``, ``--graph``, ``--graph-shapes``, ``--eval-batch-size``,
-``--eval-pad-multiple``, ``--eval-workers``).
+``--eval-pad-multiple``, ``--eval-workers``, ``--nms``, ``--nms-threshold``, ``--soft-nms-sigma``,
+``--soft-nms-min-score``).
 
 Orchestration follows ``main()`` (``train.py:383-450``): init the data-parallel runtime
 (``hvd.init()``), backbone object, generators, model (snapshot or weights), summary, callbacks
@@ -60,6 +61,7 @@ def check_args(parsed_args):
     resolve_classification_loss(parsed_args)
     resolve_head_norm(parsed_args)
     resolve_regression_bins(parsed_args)
+    resolve_nms(parsed_args)
     if getattr(parsed_args, "warmup_epochs", 0) < 0:
         raise SystemExit("--warmup-epochs must be >= 0")
     if not 0.0 <= getattr(parsed_args, "ema_decay", 0.0) < 1.0:
@@ -243,6 +245,35 @@ def regression_bins_kwargs(parsed_args):
     return dict(regression_bins=parsed_args.regression_bins, regression_range=parsed_args.regression_range)
 
 
+def resolve_nms(parsed_args):
+    """``--nms`` and its paired flags.  The choice has no state: it shapes the prediction model only."""
+    if not hasattr(parsed_args, "nms"):
+        return parsed_args
+    soft = parsed_args.nms != "hard"
+    if not soft and (parsed_args.soft_nms_sigma is not None or parsed_args.soft_nms_min_score is not None):
+        raise SystemExit("--soft-nms-sigma and --soft-nms-min-score go with --nms soft-linear or soft-gaussian; hard "
+                         "NMS decays no score")
+    if parsed_args.soft_nms_sigma is not None and not parsed_args.soft_nms_sigma > 0:
+        raise SystemExit("--soft-nms-sigma must be > 0, got {}".format(parsed_args.soft_nms_sigma))
+    if parsed_args.soft_nms_min_score is not None and parsed_args.soft_nms_min_score < 0:
+        raise SystemExit("--soft-nms-min-score must be >= 0, got {}".format(parsed_args.soft_nms_min_score))
+    if not 0.0 <= parsed_args.nms_threshold <= 1.0:
+        raise SystemExit("--nms-threshold must be in [0, 1], got {}".format(parsed_args.nms_threshold))
+    return parsed_args
+
+
+def nms_kwargs(parsed_args):
+    """The prediction model's keywords of the resolved ``--nms`` flags (none without them: the model's defaults)."""
+    kw = {}
+    if getattr(parsed_args, "nms_threshold", 0.5) != 0.5:
+        kw["nms_threshold"] = parsed_args.nms_threshold
+    if getattr(parsed_args, "nms", "hard") != "hard":
+        kw["nms_kind"] = parsed_args.nms[len("soft-"):]
+        kw["soft_nms_sigma"] = 0.5 if parsed_args.soft_nms_sigma is None else parsed_args.soft_nms_sigma
+        kw["soft_nms_min_score"] = parsed_args.soft_nms_min_score
+    return kw
+
+
 def resolve_assigner(parsed_args):
     """``--assigner`` / ``--atss-topk`` when given, else what ``--snapshot`` stores, else iou and 9.  The assignment
     has no state, so a flag that differs from the snapshot wins, with a warning."""
@@ -415,6 +446,19 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--dfl-weight", type=float, default=None, metavar="W",
                         help="With --regression-bins: weight of the Distribution Focal Loss (default 0.25, or what "
                              "--snapshot stores).")
+    parser.add_argument("--nms", choices=["hard", "soft-linear", "soft-gaussian"], default="hard",
+                        help="Per-class suppression of the prediction model the evaluation callbacks run.  hard "
+                             "(default): greedy NMS at --nms-threshold.  soft-linear / soft-gaussian: Soft-NMS (Bodla "
+                             "et al. 2017) on the device -- an overlapping box's score decays by 1 - IoU above "
+                             "--nms-threshold, or by exp(-IoU^2 / --soft-nms-sigma), and it stays in play until it "
+                             "falls to --soft-nms-min-score.  No state: nothing is written into snapshots.")
+    parser.add_argument("--nms-threshold", type=float, default=0.5, metavar="T",
+                        help="IoU threshold of hard NMS and of the linear Soft-NMS decay (default 0.5).")
+    parser.add_argument("--soft-nms-sigma", type=float, default=None, metavar="S",
+                        help="With --nms soft-gaussian: the decay's sigma (default 0.5).")
+    parser.add_argument("--soft-nms-min-score", type=float, default=None, metavar="M",
+                        help="With a soft --nms: a box whose decayed score falls to M is dropped (default: the "
+                             "prediction model's score threshold, 0.05).")
     parser.add_argument("--assigner", choices=["iou", "atss"], default=None,
                         help="Anchor target assignment.  iou (default): the reference's fixed thresholds (IoU >= 0.5 "
                              "positive, 0.4-0.5 ignored).  atss: adaptive training sample selection -- every box takes "
@@ -735,7 +779,7 @@ def main(args=None):
         runtime.shutdown()
         return 0
 
-    prediction_model = models.retinanet_bbox(model=model)
+    prediction_model = models.retinanet_bbox(model=model, **nms_kwargs(args))
     prediction_model.compute_dtype = dtype
     callbacks = create_callbacks(trainer, prediction_model, validation_generator, args)
     verbose = 1 if (rank == 0 or args.log_all_ranks) else 0

@@ -315,8 +315,11 @@ class RetinaNetBBox(nn.Module):
     """
 
     def __init__(self, model: RetinaNet, nms: bool = True, class_specific_filter: bool = True,
-                 nms_threshold: float = 0.5, score_threshold: float = 0.05, max_detections: int = 300):
+                 nms_threshold: float = 0.5, score_threshold: float = 0.05, max_detections: int = 300,
+                 nms_kind: str = "hard", soft_nms_sigma: float = 0.5, soft_nms_min_score: Optional[float] = None):
         super().__init__()
+        box_ops.check_nms_kind(nms_kind, soft_nms_sigma, soft_nms_min_score, score_threshold)
+        self.soft_nms = dict(nms_kind=nms_kind, soft_nms_sigma=soft_nms_sigma, soft_nms_min_score=soft_nms_min_score)
         self.model = model
         self.nms = nms
         self.class_specific_filter = class_specific_filter
@@ -334,16 +337,19 @@ class RetinaNetBBox(nn.Module):
         if (self.nms and self.class_specific_filter and images.is_cuda and native.available()
                 and self.max_detections <= 512):
             # batched device path: threshold + per-class NMS for the whole batch in two launches,
-            # decode + clip fused (only candidates are decoded), one top-k (csrc/kernels/filter.hip)
+            # decode + clip fused (only candidates are decoded), one top-k (csrc/kernels/filter.hip; the soft
+            # kinds: csrc/kernels/soft_nms.hip)
             return native.filter_detections_batched(anchors, out["regression"], out["classification"], H, W,
-                                                    self.score_threshold, self.nms_threshold, self.max_detections)
+                                                    self.score_threshold, self.nms_threshold, self.max_detections,
+                                                    **self.soft_nms)
         boxes = box_ops.bbox_transform_inv(anchors[None], out["regression"].float())
         boxes = box_ops.clip_boxes(boxes, H, W)
         cls = torch.sigmoid(out["classification"].float())
         res_b, res_s, res_l = [], [], []
         for i in range(images.shape[0]):
             b, s, l = box_ops.filter_detections(boxes[i], cls[i], self.nms, self.class_specific_filter,
-                                                self.nms_threshold, self.score_threshold, self.max_detections)
+                                                self.nms_threshold, self.score_threshold, self.max_detections,
+                                                **self.soft_nms)
             res_b.append(b)
             res_s.append(s)
             res_l.append(l)

@@ -121,11 +121,66 @@ def nms(boxes: torch.Tensor, scores: torch.Tensor, iou_threshold: float, max_out
     return order[torch.tensor(keep, dtype=torch.long, device=boxes.device)]
 
 
+SOFT_NMS_KINDS = ("linear", "gaussian")
+
+
+def check_nms_kind(nms_kind: str, sigma: float, min_score: Optional[float], score_threshold: float) -> float:
+    """Validate ``(nms_kind, sigma, min_score)``; returns the score floor (``score_threshold`` when none is given)."""
+    if nms_kind not in ("hard",) + SOFT_NMS_KINDS:
+        raise ValueError("nms_kind must be hard, linear or gaussian, got {!r}".format(nms_kind))
+    floor = float(score_threshold if min_score is None else min_score)
+    if nms_kind != "hard" and not float(sigma) > 0:
+        raise ValueError("soft_nms_sigma must be > 0, got {}".format(sigma))
+    if nms_kind != "hard" and floor < 0:
+        raise ValueError("soft_nms_min_score must be >= 0, got {}".format(floor))
+    return floor
+
+
+def soft_nms(boxes: torch.Tensor, scores: torch.Tensor, kind: str, iou_threshold: float = 0.5, sigma: float = 0.5,
+             min_score: float = 0.05, max_output: int = 300) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Soft-NMS (Bodla et al., ICCV 2017) of one (image, class) segment, in the dtype of ``boxes`` / ``scores``: fp32 is
+    the CPU path and the fallback, float64 the oracle of ``csrc/kernels/soft_nms.hip``.
+
+    Until ``max_output`` boxes are emitted: pick the live candidate of largest current score (an exact tie goes to the
+    lower index); stop if that score ``<= min_score``; emit it and mark it dead; multiply every other live score by
+    ``w(u)``, ``u`` its IoU (:func:`box_iou_plain`) with the pick -- ``linear``: ``1 - u`` where ``u > iou_threshold``,
+    else exactly 1; ``gaussian``: ``exp(-(u * u) / sigma)`` -- and a score that falls to ``<= min_score`` is dead from
+    then on.  Returns (indices into ``boxes`` in emission order, their decayed scores)."""
+    if kind not in SOFT_NMS_KINDS:
+        raise ValueError("soft_nms: kind must be linear or gaussian, got {!r}".format(kind))
+    check_nms_kind(kind, sigma, min_score, min_score)
+    s = scores.clone()             # a dead candidate has score 0
+    zero = torch.zeros_like(s)
+    idx, out = [], []
+    for _ in range(min(int(max_output), s.numel())):
+        i = int(torch.argmax(s))    # the first maximal value: the lower index on a tie
+        top = s[i]
+        if not bool(top > min_score):
+            break
+        idx.append(i)
+        out.append(top)
+        u = box_iou_plain(boxes[i:i + 1], boxes)[0]
+        if kind == "linear":
+            w = torch.where(u > iou_threshold, 1 - u, torch.ones_like(u))
+        else:
+            w = torch.exp(-(u * u) / sigma)
+        s = s * w
+        s[i] = 0
+        s = torch.where(s > min_score, s, zero)
+    if not idx:
+        return torch.zeros(0, dtype=torch.long, device=boxes.device), scores.new_zeros(0)
+    return torch.tensor(idx, dtype=torch.long, device=boxes.device), torch.stack(out)
+
+
 def filter_detections(boxes: torch.Tensor, classification: torch.Tensor, nms_enabled: bool = True,
                       class_specific_filter: bool = True, nms_threshold: float = 0.5,
                       score_threshold: float = 0.05, max_detections: int = 300,
-                      backend: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+                      backend: Optional[str] = None, nms_kind: str = "hard", soft_nms_sigma: float = 0.5,
+                      soft_nms_min_score: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Per-image FilterDetections.  boxes (A, 4), classification (A, C) probabilities.
+
+    ``nms_kind`` linear / gaussian replaces the greedy NMS by :func:`soft_nms` (torch on every backend here; the
+    device form is ``native.filter_detections_batched``) and ranks across classes by the decayed scores.
 
     Returns boxes (max_det, 4), scores (max_det,), labels (max_det,) padded with -1.
     """
@@ -133,8 +188,21 @@ def filter_detections(boxes: torch.Tensor, classification: torch.Tensor, nms_ena
     if backend is None:
         backend = "hip" if (boxes.is_cuda and native.available()) else "torch"
     dev = boxes.device
-    all_idx, all_lab = [], []
-    if class_specific_filter:
+    floor = check_nms_kind(nms_kind, soft_nms_sigma, soft_nms_min_score, score_threshold)
+    all_idx, all_lab, all_sc = [], [], None      # all_sc: the decayed scores of a soft kind
+    if nms_kind != "hard" and nms_enabled:
+        if class_specific_filter:
+            segments = [(classification[:, c], c) for c in range(classification.shape[1])]
+        else:
+            segments = [classification.max(dim=1)]
+        all_sc = []
+        for s, lab in segments:
+            idx = torch.nonzero(s > score_threshold).flatten()
+            k, sc = soft_nms(boxes[idx], s[idx], nms_kind, nms_threshold, soft_nms_sigma, floor, max_detections)
+            all_idx.append(idx[k])
+            all_sc.append(sc)
+            all_lab.append(lab[idx[k]] if torch.is_tensor(lab) else torch.full_like(k, lab))
+    elif class_specific_filter:
         C = classification.shape[1]
         for c in range(C):
             s = classification[:, c]
@@ -164,10 +232,11 @@ def filter_detections(boxes: torch.Tensor, classification: torch.Tensor, nms_ena
         idx = torch.cat(all_idx)
         lab = torch.cat(all_lab)
         if idx.numel():
-            sc = classification[idx, lab]
+            sc = classification[idx, lab] if all_sc is None else torch.cat(all_sc)
             k = min(max_detections, sc.numel())
             top_s, top_i = torch.topk(sc, k)
             out_b[:k] = boxes[idx[top_i]].float()
             out_s[:k] = top_s.float()
             out_l[:k] = lab[top_i].to(torch.int32)
     return out_b, out_s, out_l
+

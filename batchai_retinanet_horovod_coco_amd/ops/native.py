@@ -98,6 +98,9 @@ _SIGS = {
     "mxr_filter_select": [c_vp, c_int, c_int, c_int, c_int, c_float, c_vp, c_vp, c_int, c_vp],
     "mxr_filter_nms": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_int, c_int, c_int, c_float, c_float,
                        c_float, c_float, c_int, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "mxr_filter_soft_nms": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_float, c_vp, c_vp, c_vp, c_vp, c_vp,
+                            c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_float, c_float, c_float, c_int,
+                            c_vp, c_vp, c_vp, c_vp, c_vp],
     "mxr_conv_geom_size": [],
     "mxr_s2_stack_flip": [c_vp, c_vp, c_int, c_int, c_vp, c_vp],
     "mxr_conv_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(ConvGeom), c_int, c_int, c_int, c_vp],
@@ -1342,17 +1345,30 @@ def nms(boxes: torch.Tensor, scores: torch.Tensor, thr: float, max_out: int) -> 
 
 
 FILTER_CAP = 4096
+SOFT_NMS_CAP = 4096     # soft_nms.hip: 16 register slots x 256 threads
 
 
 def filter_detections_batched(anchors: torch.Tensor, deltas: torch.Tensor, cls_logits: torch.Tensor, H: float,
                               W: float, score_threshold: float = 0.05, nms_threshold: float = 0.5,
-                              max_detections: int = 300, box_std: float = 0.2, cap: int = FILTER_CAP):
+                              max_detections: int = 300, box_std: float = 0.2, cap: int = FILTER_CAP,
+                              nms_kind: str = "hard", soft_nms_sigma: float = 0.5,
+                              soft_nms_min_score: Optional[float] = None):
     """Class-specific FilterDetections for a whole batch on the device (csrc/kernels/filter.hip).
 
     anchors (A, 4) fp32, deltas (B, A, 4), cls_logits (B, A, C) bf16/fp32 LOGITS (sigmoid applied in the
     kernel).  Returns boxes (B, D, 4), scores (B, D), labels (B, D) int32 padded with -1 (D = max_detections).
     Two launches per batch (select, per-(image, class) sort + greedy NMS) and one torch.topk; the only host
-    sync is the overflow check (an (image, class) with more than ``cap`` candidates is re-run exactly)."""
+    sync is the overflow check (an (image, class) with more than ``cap`` candidates is re-run exactly).
+
+    ``nms_kind`` linear / gaussian runs Soft-NMS (csrc/kernels/soft_nms.hip; the rule is ``ops.boxes.soft_nms``) in
+    place of the greedy stage: scores decay by ``1 - IoU`` above ``nms_threshold`` or by ``exp(-IoU^2 /
+    soft_nms_sigma)``, die at ``soft_nms_min_score`` (default: ``score_threshold``), and the top-k ranks the decayed
+    scores.  Its candidates live in registers, so ``cap`` may not exceed ``SOFT_NMS_CAP``."""
+    from .boxes import check_nms_kind
+    floor = check_nms_kind(nms_kind, soft_nms_sigma, soft_nms_min_score, score_threshold)
+    if nms_kind != "hard" and cap > SOFT_NMS_CAP:
+        raise ValueError("filter_detections_batched: nms_kind {} holds at most {} candidates per (image, class) in "
+                         "registers, got cap = {}".format(nms_kind, SOFT_NMS_CAP, cap))
     B, A, C = cls_logits.shape
     dev = cls_logits.device
     D = int(max_detections)
@@ -1374,10 +1390,26 @@ def filter_detections_batched(anchors: torch.Tensor, deltas: torch.Tensor, cls_l
     ddt = 1 if deltas.dtype == torch.bfloat16 else 0
     if ddt == 0 and deltas.dtype != torch.float32:
         deltas = deltas.float()
-    _chk(lib().mxr_filter_nms(_p(cand), _p(cnt), cap, 0, 0, B * Cp, _p(anchors), _p(deltas), ddt, A, Cp, float(H),
-                              float(W), float(box_std), float(nms_threshold), D, _p(out_s), _p(out_b), _p(out_n),
-                              _p(ovf), _s()), "filter_nms")
-    if bool(ovf.any()):
+    if nms_kind != "hard":
+        def soft(exact, seg, ws):
+            _chk(lib().mxr_filter_soft_nms(_p(cand), _p(cnt), cap, exact, seg, B * Cp, _p(cls_logits),
+                                           1 if cls_logits.dtype == torch.bfloat16 else 0, float(score_threshold),
+                                           _p(ws[0]), _p(ws[1]), _p(ws[2]), _p(anchors), _p(deltas), ddt, A, Cp,
+                                           float(H), float(W), float(box_std), 1 if nms_kind == "linear" else 2,
+                                           float(nms_threshold), float(soft_nms_sigma), floor, D, _p(out_s), _p(out_b),
+                                           _p(out_n), _p(ovf), _s()), "filter_soft_nms")
+        soft(0, 0, (None, None, None))
+        if bool(ovf.any()):
+            # exact path for crowded (image, class) pairs: one workgroup each, its state in this workspace
+            ws = (torch.empty((A, 4), dtype=torch.float32, device=dev),
+                  torch.empty(A, dtype=torch.float32, device=dev), torch.empty(A, dtype=torch.int32, device=dev))
+            for seg in torch.nonzero(ovf).flatten().tolist():
+                soft(1, seg, ws)
+    else:
+        _chk(lib().mxr_filter_nms(_p(cand), _p(cnt), cap, 0, 0, B * Cp, _p(anchors), _p(deltas), ddt, A, Cp, float(H),
+                                  float(W), float(box_std), float(nms_threshold), D, _p(out_s), _p(out_b), _p(out_n),
+                                  _p(ovf), _s()), "filter_nms")
+    if nms_kind == "hard" and bool(ovf.any()):
         # exact path for crowded (image, class) pairs: full candidate list, sorted on the device
         for seg in torch.nonzero(ovf).flatten().tolist():
             b, c = divmod(seg, Cp)

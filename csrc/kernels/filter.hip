@@ -17,34 +17,11 @@
 //   so far by all four waves, the intra-chunk suppression is a 64 x 64 bit matrix, and one lane walks the
 //   64 bits in score order.  A segment whose count exceeded the capacity is re-run by the host exactly
 //   (its full candidate list sorted on the device and fed through the same kernel, sorted-input mode).
-#include "common.h"
-
-// decode, IoU and sigmoid follow the oracle's operation order with IEEE rounding and no FMA contraction,
-// so that NMS decisions on near-ties match the torch oracle (ops/boxes.py)
-#pragma clang fp contract(off)
+#include "filter_common.h"
 
 namespace {
 
-constexpr int FD_BLOCK = 256;
 constexpr int FD_CAP_MAX = 8192;     // keys per segment held in LDS (64 KiB)
-constexpr int FD_MAXDET = 512;
-
-__device__ __forceinline__ float fd_iou(const float4 a, const float4 b) {
-  const float aa = fmaxf(a.z - a.x, 0.f) * fmaxf(a.w - a.y, 0.f);
-  const float ab = fmaxf(b.z - b.x, 0.f) * fmaxf(b.w - b.y, 0.f);
-  const float iw = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.f);
-  const float ih = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.f);
-  const float inter = iw * ih;
-  const float u = aa + ab - inter;
-  return u > 0.f ? __fdiv_rn(inter, u) : 0.f;
-}
-
-__device__ __forceinline__ float fd_sigmoid(float x) { return __fdiv_rn(1.f, 1.f + expf(-x)); }
-
-// scores in (0, 1): the float bits order like the values
-__device__ __forceinline__ unsigned long long fd_key(float p, int a) {
-  return ((unsigned long long)__float_as_uint(p) << 32) | (unsigned long long)(0xffffffffu - (unsigned)a);
-}
 
 template <typename T>
 __global__ __launch_bounds__(FD_BLOCK) void filter_select_kernel(const T* __restrict__ cls, long long nvec,
@@ -144,23 +121,8 @@ __global__ __launch_bounds__(FD_BLOCK) void filter_nms_kernel(
       float sc = -1.f;
       if (s + tid < n) {
         const unsigned long long key = sorted ? src[s + tid] : keys[s + tid];
-        const int a = (int)(0xffffffffu - (unsigned)(key & 0xffffffffull));
-        sc = __uint_as_float((unsigned)(key >> 32));
-        const float4 an = reinterpret_cast<const float4*>(anchors)[a];
-        const long long di = ((long long)b * A + a) * 4;
-        float d[4];
-        if (ddtype == 1) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) d[j] = bf2f(((const bf16_t*)deltas)[di + j]);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) d[j] = ((const float*)deltas)[di + j];
-        }
-        const float aw = an.z - an.x, ah = an.w - an.y;
-        bx.x = fminf(fmaxf(an.x + d[0] * box_std * aw, 0.f), W);
-        bx.y = fminf(fmaxf(an.y + d[1] * box_std * ah, 0.f), H);
-        bx.z = fminf(fmaxf(an.z + d[2] * box_std * aw, 0.f), W);
-        bx.w = fminf(fmaxf(an.w + d[3] * box_std * ah, 0.f), H);
+        sc = fd_key_score(key);
+        bx = fd_decode(anchors, deltas, ddtype, b, fd_key_anchor(key), A, box_std, H, W);
       }
       cbox[tid] = bx;
       cscore[tid] = sc;
