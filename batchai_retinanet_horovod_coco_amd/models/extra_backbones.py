@@ -15,7 +15,9 @@ Layer names follow keras.applications so ``--weights`` by-name loading lines up:
 
 As in keras.applications, BN in MobileNet/DenseNet is ordinary (trainable, batch statistics in
 training).  VGG convs run through the same conv front-end as ResNet (HIP implicit GEMM when the
-shape class is covered); depthwise and BN-heavy backbones use PyTorch/MIOpen ops.
+shape class is covered).  MobileNet's 13 depthwise 3x3 convs run on the HIP kernels of ``csrc/kernels/dwconv.hip``
+(``ops.depthwise``) for bf16 activations on the GPU; its batch-norms, ReLU6, 1x1 convs and stem, and all of DenseNet,
+use PyTorch/MIOpen ops.
 """
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..ops import depthwise as dw_ops
 from .layers import Conv2D
 
 
@@ -145,17 +148,36 @@ class MobileNet(nn.Module, _ShapeProbe):
             self.strides.append(s)
             c = f
         self.out_channels = [0, int(256 * alpha), int(512 * alpha), int(1024 * alpha)]
+        # 'auto': dwconv.hip where it serves the layer (bf16 on the GPU), else the torch ops; 'torch': the torch ops;
+        # 'native': the kernels or an error
+        self.dw_backend = "auto"
+        self.dw_taken = []       # per layer of the last forward: 'native' or 'torch'
+
+    def _depthwise(self, i, x):
+        """conv_dw_{i+1} on NCHW ``x``: the kernels on its NHWC view (no pad, no copy once ``x`` is channels-last), or
+        the torch ops."""
+        s = self.strides[i]
+        xh = x.permute(0, 2, 3, 1)
+        if self.dw_backend == "native" or dw_ops.takes_native(xh, s, self.dw_backend):
+            self.dw_taken.append("native")
+            return _nchw(dw_ops.depthwise_conv3x3(xh, self.dw[i].weight, s, self.dw_backend))
+        self.dw_taken.append("torch")
+        x = F.pad(x, (1, 1, 1, 1)) if s == 1 else F.pad(x, (0, 1, 0, 1))
+        return self.dw[i](x)
 
     def forward(self, x):
         dt = x.dtype
+        self.dw_taken = []
         with _autocast(x):
             x = _nchw(x)
             x = F.pad(x, (0, 1, 0, 1))                   # keras: ZeroPadding2D(((0,1),(0,1))) + valid s2
             x = self.conv1_bn(self.conv1(x))
+            if self.dw_backend == "native" or dw_ops.takes_native(x.permute(0, 2, 3, 1), 1, self.dw_backend):
+                # once: BN, ReLU6 and the 1x1 convs keep the format, so the NHWC views below are no copies
+                x = x.contiguous(memory_format=torch.channels_last)
             outs = []
             for i in range(13):
-                x = F.pad(x, (1, 1, 1, 1)) if self.strides[i] == 1 else F.pad(x, (0, 1, 0, 1))
-                x = self.dw_bn[i](self.dw[i](x))
+                x = self.dw_bn[i](self._depthwise(i, x))
                 x = self.pw_bn[i](self.pw[i](x))
                 if i + 1 in (5, 11, 13):
                     outs.append(_nhwc(x).to(dt))

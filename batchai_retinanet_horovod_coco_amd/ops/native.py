@@ -178,6 +178,10 @@ _SIGS = {
     "mxr_s2_stack": [c_vp, c_vp, c_int, c_int, c_vp, c_vp],
     "mxr_pyr_pack": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp],
     "mxr_pyr_pack_f8": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_float, c_vp],
+    "mxr_dwconv3x3_fwd": [c_vp] * 3 + [c_int] * 10 + [c_vp],
+    "mxr_dwconv3x3_dgrad": [c_vp] * 3 + [c_int] * 10 + [c_vp],
+    "mxr_dwconv_wgrad_work": [c_int] * 4,
+    "mxr_dwconv3x3_wgrad": [c_vp] * 4 + [c_ll] + [c_int] * 10 + [c_vp],
     "mxr_host_register": [c_vp, c_ll],
     "mxr_host_unregister": [c_vp],
 }
@@ -711,6 +715,117 @@ class GroupNormReluPackedFn(torch.autograd.Function):
         shapes, groups, gdt, bdt = ctx.cfg
         dx, dgamma, dbeta = gn_relu_bwd(dy, x, shapes, g32, b32, mean, rstd, groups)
         return dx, dgamma.to(gdt), dbeta.to(bdt), None, None, None
+
+
+# =========================================================================================
+# depthwise 3x3 convolution on NHWC bf16 (dwconv.hip)
+# =========================================================================================
+def dwconv_geometry(H: int, W: int, stride: int):
+    """(pad_top, pad_left, Ho, Wo) of the Keras MobileNet depthwise layers: stride 1 pads one pixel on every side,
+    stride 2 pads one pixel at the bottom and right only and takes a valid window."""
+    if stride == 1:
+        return 1, 1, int(H), int(W)
+    if stride != 2 or H < 2 or W < 2:
+        raise ValueError("depthwise 3x3: stride 1, or stride 2 on at least 2 x 2 pixels, expected")
+    return 0, 0, (int(H) - 2) // 2 + 1, (int(W) - 2) // 2 + 1
+
+
+def dwconv_served(x: torch.Tensor, stride: int) -> bool:
+    """What ``dwconv.hip`` serves: bf16 ``[N, H, W, C]`` on the GPU, ``C % 8 == 0``, stride 1 or 2 (the entry points'
+    own rule, mirrored so that a caller can decide before allocating)."""
+    return (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16 and x.shape[3] >= 8 and x.shape[3] % 8 == 0
+            and 1 <= x.shape[0] <= 65535 and (stride == 1 or (stride == 2 and x.shape[1] >= 2 and x.shape[2] >= 2))
+            and (not x.is_contiguous() or x.data_ptr() % 16 == 0))
+
+
+def dwconv_taps(weight: torch.Tensor) -> torch.Tensor:
+    """The tap-major ``[9][C]`` fp32 table of a ``(C, 1, 3, 3)`` depthwise parameter."""
+    if weight.dim() != 4 or tuple(weight.shape[1:]) != (1, 3, 3):
+        raise ValueError("depthwise 3x3: a (C, 1, 3, 3) weight expected, got {}".format(tuple(weight.shape)))
+    return weight.detach().reshape(weight.shape[0], 9).t().float().contiguous()
+
+
+def _dw_dt(t: torch.Tensor) -> int:
+    return {torch.float32: 0, torch.bfloat16: 1}.get(t.dtype, 2)
+
+
+def _dw_call(name, fn, *args):
+    rc = fn(*args)
+    if rc == -1:
+        raise NotServed(name)
+    _chk(rc, name)
+
+
+def dwconv3x3_fwd(x, w9, stride):
+    """``y`` bf16 ``[N, Ho, Wo, C]`` of NHWC ``x`` and the ``[9][C]`` fp32 taps; raises :class:`NotServed`."""
+    if not dwconv_served(x, stride) or tuple(w9.shape) != (9, x.shape[3]):
+        raise NotServed("dwconv3x3_fwd")    # decided before anything is allocated (the entry point judges again)
+    x = x.contiguous()
+    N, H, W, C = x.shape
+    pt, pl, Ho, Wo = dwconv_geometry(H, W, stride)
+    y = torch.empty((N, Ho, Wo, C), dtype=x.dtype, device=x.device)
+    _dw_call("dwconv3x3_fwd", lib().mxr_dwconv3x3_fwd, _p(x), _p(w9), _p(y), N, H, W, C, stride, pt, pl, Ho, Wo,
+             _dw_dt(x), _s())
+    return y
+
+
+def dwconv3x3_dgrad(dy, w9, x_shape, stride):
+    """``dx`` bf16 ``x_shape`` (every element written once) of NHWC ``dy``."""
+    N, H, W, C = (int(s) for s in x_shape)
+    if not dwconv_served(dy, 1) or tuple(w9.shape) != (9, C) or stride not in (1, 2) or (stride == 2 and min(H, W) < 2):
+        raise NotServed("dwconv3x3_dgrad")
+    pt, pl, Ho, Wo = dwconv_geometry(H, W, stride)
+    if tuple(dy.shape) != (N, Ho, Wo, C):
+        raise ValueError("dwconv3x3_dgrad: dy {} does not match x {}".format(tuple(dy.shape), (N, H, W, C)))
+    dy = dy.contiguous()
+    dx = torch.empty((N, H, W, C), dtype=dy.dtype, device=dy.device)
+    _dw_call("dwconv3x3_dgrad", lib().mxr_dwconv3x3_dgrad, _p(dy), _p(w9), _p(dx), N, H, W, C, stride, pt, pl, Ho, Wo,
+             _dw_dt(dy), _s())
+    return dx
+
+
+def dwconv3x3_wgrad(dy, x, stride):
+    """``dw9`` fp32 ``[9][C]``: per tap and channel, the sum over the ``N * Ho * Wo`` output pixels of ``dy * x``."""
+    if not dwconv_served(x, stride) or not dwconv_served(dy, 1):
+        raise NotServed("dwconv3x3_wgrad")
+    x = x.contiguous()
+    N, H, W, C = x.shape
+    pt, pl, Ho, Wo = dwconv_geometry(H, W, stride)
+    if tuple(dy.shape) != (N, Ho, Wo, C):
+        raise ValueError("dwconv3x3_wgrad: dy {} does not match x {}".format(tuple(dy.shape), (N, H, W, C)))
+    dy = dy.contiguous()
+    nwork = lib().mxr_dwconv_wgrad_work(N, Ho, Wo, C)
+    if nwork <= 0:
+        raise NotServed("dwconv3x3_wgrad")
+    dw9 = torch.empty((9, C), dtype=torch.float32, device=x.device)
+    work = torch.empty(nwork, dtype=torch.float32, device=x.device)
+    _dw_call("dwconv3x3_wgrad", lib().mxr_dwconv3x3_wgrad, _p(dy), _p(x), _p(dw9), _p(work), nwork, N, H, W, C, stride,
+             pt, pl, Ho, Wo, _dw_dt(x), _s())
+    return dw9
+
+
+class DepthwiseConv3x3Fn(torch.autograd.Function):
+    """Depthwise 3x3 conv of NHWC bf16 ``x`` with a ``(C, 1, 3, 3)`` weight; saves x and the tap table."""
+
+    @staticmethod
+    def forward(ctx, x, weight, stride):
+        x = x.contiguous()
+        w9 = dwconv_taps(weight)
+        y = dwconv3x3_fwd(x, w9, stride)
+        ctx.save_for_backward(x, w9)
+        ctx.cfg = (int(stride), weight.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w9 = ctx.saved_tensors
+        stride, wdt = ctx.cfg
+        dy = dy.to(x.dtype)
+        dx = dwconv3x3_dgrad(dy, w9, x.shape, stride) if ctx.needs_input_grad[0] else None
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dw = dwconv3x3_wgrad(dy, x, stride).t().reshape(x.shape[3], 1, 3, 3).to(wdt)
+        return dx, dw, None
 
 
 # =========================================================================================
