@@ -16,8 +16,8 @@ Layer names follow keras.applications so ``--weights`` by-name loading lines up:
 As in keras.applications, BN in MobileNet/DenseNet is ordinary (trainable, batch statistics in
 training).  VGG convs run through the same conv front-end as ResNet (HIP implicit GEMM when the
 shape class is covered).  MobileNet's 13 depthwise 3x3 convs run on the HIP kernels of ``csrc/kernels/dwconv.hip``
-(``ops.depthwise``) for bf16 activations on the GPU; its batch-norms, ReLU6, 1x1 convs and stem, and all of DenseNet,
-use PyTorch/MIOpen ops.
+(``ops.depthwise``) and its 27 batch-norms + ReLU6 on those of ``csrc/kernels/batch_norm.hip`` (``ops.norm``) for bf16
+activations on the GPU; its 1x1 convs and stem and all of DenseNet (which concatenates in NCHW) use PyTorch/MIOpen ops.
 """
 from __future__ import annotations
 
@@ -28,6 +28,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops import depthwise as dw_ops
+from ..ops import norm as norm_ops
 from .layers import Conv2D
 
 
@@ -119,7 +120,19 @@ class _BNAct(nn.Module):
         self.bn = nn.BatchNorm2d(c, eps=eps, momentum=momentum)
         self.act = act
 
-    def forward(self, x):    # NCHW
+    def forward(self, x, backend="torch", taken=None):    # NCHW
+        """``backend`` other than 'torch': the kernels of batch_norm.hip on the NHWC view where they serve it (no copy
+        once ``x`` is channels-last); ``self.bn`` stays the holder of parameters and buffers.  ``taken`` collects the
+        path."""
+        xh = x.permute(0, 2, 3, 1)
+        native = backend == "native" or norm_ops.bn_takes_native(xh, self.bn.training, backend)
+        if taken is not None:
+            taken.append("native" if native else "torch")
+        if native:
+            y = norm_ops.batch_norm_act(xh, self.bn, self.bn.training, self.act, backend)
+            if self.bn.training:
+                self.bn.num_batches_tracked.add_(1)      # on the device, as nn.BatchNorm2d does
+            return _nchw(y)
         x = self.bn(x)
         if self.act == "relu6":
             return F.relu6(x)
@@ -152,6 +165,10 @@ class MobileNet(nn.Module, _ShapeProbe):
         # 'native': the kernels or an error
         self.dw_backend = "auto"
         self.dw_taken = []       # per layer of the last forward: 'native' or 'torch'
+        # the same three for batch_norm.hip, and the path of the 27 norms in forward order (the layer timings behind
+        # 'auto' are profiles/batchnorm.txt)
+        self.bn_backend = "auto"
+        self.bn_taken = []
 
     def _depthwise(self, i, x):
         """conv_dw_{i+1} on NCHW ``x``: the kernels on its NHWC view (no pad, no copy once ``x`` is channels-last), or
@@ -167,18 +184,24 @@ class MobileNet(nn.Module, _ShapeProbe):
 
     def forward(self, x):
         dt = x.dtype
-        self.dw_taken = []
+        self.dw_taken, self.bn_taken = [], []
+        bn = (self.bn_backend, self.bn_taken)
         with _autocast(x):
             x = _nchw(x)
             x = F.pad(x, (0, 1, 0, 1))                   # keras: ZeroPadding2D(((0,1),(0,1))) + valid s2
-            x = self.conv1_bn(self.conv1(x))
+            x = self.conv1(x)
+            xh = x.permute(0, 2, 3, 1)
+            if self.bn_backend == "native" or norm_ops.bn_takes_native(xh, self.training, self.bn_backend):
+                # once, in front of the first norm: all 27 are served on NHWC views that are no copies
+                x = x.contiguous(memory_format=torch.channels_last)
+            x = self.conv1_bn(x, *bn)
             if self.dw_backend == "native" or dw_ops.takes_native(x.permute(0, 2, 3, 1), 1, self.dw_backend):
                 # once: BN, ReLU6 and the 1x1 convs keep the format, so the NHWC views below are no copies
                 x = x.contiguous(memory_format=torch.channels_last)
             outs = []
             for i in range(13):
-                x = self.dw_bn[i](self._depthwise(i, x))
-                x = self.pw_bn[i](self.pw[i](x))
+                x = self.dw_bn[i](self._depthwise(i, x), *bn)
+                x = self.pw_bn[i](self.pw[i](x), *bn)
                 if i + 1 in (5, 11, 13):
                     outs.append(_nhwc(x).to(dt))
         return outs

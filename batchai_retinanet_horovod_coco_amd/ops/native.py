@@ -182,6 +182,11 @@ _SIGS = {
     "mxr_dwconv3x3_dgrad": [c_vp] * 3 + [c_int] * 10 + [c_vp],
     "mxr_dwconv_wgrad_work": [c_int] * 4,
     "mxr_dwconv3x3_wgrad": [c_vp] * 4 + [c_ll] + [c_int] * 10 + [c_vp],
+    "mxr_bn_chunk_rows": [c_int],
+    "mxr_bn_work": [c_ll, c_int],
+    "mxr_bn_stats": [c_vp] * 6 + [c_ll, c_ll, c_int, c_float, c_float, c_int, c_int, c_vp],
+    "mxr_bn_act_fwd": [c_vp] * 6 + [c_ll, c_int, c_int, c_int, c_vp],
+    "mxr_bn_act_bwd": [c_vp] * 10 + [c_ll, c_ll, c_int, c_int, c_int, c_int, c_vp],
     "mxr_host_register": [c_vp, c_ll],
     "mxr_host_unregister": [c_vp],
 }
@@ -826,6 +831,109 @@ class DepthwiseConv3x3Fn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dw = dwconv3x3_wgrad(dy, x, stride).t().reshape(x.shape[3], 1, 3, 3).to(wdt)
         return dx, dw, None
+
+
+# =========================================================================================
+# BatchNorm + activation on NHWC bf16 (batch_norm.hip)
+# =========================================================================================
+BN_ACTS = {"none": 0, "relu": 1, "relu6": 2}
+
+
+def bn_served(x: torch.Tensor, training: bool = False) -> bool:
+    """What ``batch_norm.hip`` serves: bf16 ``[..., C]`` on the GPU, ``C % 8 == 0``, at least two rows in training
+    (the entry points' own rule, mirrored so that a caller can decide before allocating)."""
+    C = x.shape[-1] if x.dim() >= 2 else 0
+    n = x.numel() // C if C else 0
+    return (x.is_cuda and x.dtype == torch.bfloat16 and C >= 8 and C % 8 == 0 and (2 if training else 1) <= n < 2 ** 31
+            and (not x.is_contiguous() or x.data_ptr() % 16 == 0))
+
+
+def _bn_work(n: int, C: int, dev) -> torch.Tensor:
+    nwork = lib().mxr_bn_work(n, C)
+    if nwork < 0:
+        raise NotServed("bn_work")
+    return torch.empty(max(1, nwork), dtype=torch.float32, device=dev)
+
+
+def _bn_vectors(what, x, *vs):
+    """The kernels read these through raw pointers: contiguous f32 ``[C]`` on x's device, or nothing is launched."""
+    for v in vs:
+        if v.dtype != torch.float32 or not v.is_contiguous() or v.numel() != x.shape[-1] or v.device != x.device:
+            raise ValueError("{}: contiguous f32 [C] vectors on the device of x expected".format(what))
+
+
+def bn_stats(x, running_mean, running_var, training, momentum, eps):
+    """(mean, rstd) f32 ``[C]`` of bf16 ``x [..., C]``: in training the batch statistics, with ``running_mean`` /
+    ``running_var`` (contiguous f32) updated in place by the kernel; else the running statistics' own."""
+    if not bn_served(x, training) or not x.is_contiguous():
+        raise NotServed("bn_stats")      # decided before anything is allocated (the entry point judges again)
+    _bn_vectors("bn_stats", x, running_mean, running_var)
+    C = x.shape[-1]
+    n = x.numel() // C
+    mean = torch.empty(C, dtype=torch.float32, device=x.device)
+    rstd = torch.empty_like(mean)
+    work = _bn_work(n, C, x.device) if training else None
+    _dw_call("bn_stats", lib().mxr_bn_stats, _p(x), _p(running_mean), _p(running_var), _p(mean), _p(rstd), _p(work),
+             work.numel() if training else 0, n, C, float(eps), float(momentum), int(bool(training)), _dw_dt(x), _s())
+    return mean, rstd
+
+
+def bn_act_fwd(x, gamma, beta, mean, rstd, act="relu6"):
+    """``y = bf16(clamp(gamma * (x - mean) * rstd + beta))`` like ``x``; gamma, beta, mean, rstd contiguous f32."""
+    if not bn_served(x) or not x.is_contiguous():
+        raise NotServed("bn_act_fwd")
+    _bn_vectors("bn_act_fwd", x, gamma, beta, mean, rstd)
+    C = x.shape[-1]
+    y = torch.empty_like(x)
+    _dw_call("bn_act_fwd", lib().mxr_bn_act_fwd, _p(x), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(y), x.numel() // C, C,
+             BN_ACTS[act], _dw_dt(x), _s())
+    return y
+
+
+def bn_act_bwd(dy, x, gamma, beta, mean, rstd, training, act="relu6"):
+    """Backward of :func:`bn_act_fwd` (the clamp mask recomputed from ``x``): (dx like x, dgamma, dbeta f32 [C])."""
+    if not bn_served(x) or not x.is_contiguous() or tuple(dy.shape) != tuple(x.shape):
+        raise NotServed("bn_act_bwd")
+    _bn_vectors("bn_act_bwd", x, gamma, beta, mean, rstd)
+    dy = dy.to(x.dtype).contiguous()
+    if dy.data_ptr() % 16:               # a contiguous slice at an odd offset: a fresh allocation is aligned
+        dy = dy.clone()
+    C = x.shape[-1]
+    n = x.numel() // C
+    dx = torch.empty_like(x)
+    dgamma = torch.empty(C, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty_like(dgamma)
+    work = _bn_work(n, C, x.device)
+    _dw_call("bn_act_bwd", lib().mxr_bn_act_bwd, _p(dy), _p(x), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dx),
+             _p(dgamma), _p(dbeta), _p(work), work.numel(), n, C, BN_ACTS[act], int(bool(training)), _dw_dt(x), _s())
+    return dx, dgamma, dbeta
+
+
+class BatchNormActFn(torch.autograd.Function):
+    """BatchNorm + activation of NHWC bf16 ``x``; saves x, mean, rstd and fp32 gamma / beta (no y, no mask).  In
+    training the running buffers are updated in place: they are marked dirty, which autograd allows for outputs only,
+    so the result is then ``(y, running_mean, running_var)``; in inference it is ``y``."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps, act):
+        x = x.contiguous()
+        g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+        mean, rstd = bn_stats(x, running_mean, running_var, training, momentum, eps)
+        y = bn_act_fwd(x, g32, b32, mean, rstd, act)
+        ctx.save_for_backward(x, mean, rstd, g32, b32)
+        ctx.cfg = (bool(training), act, gamma.dtype, beta.dtype)
+        if not training:
+            return y
+        ctx.mark_dirty(running_mean, running_var)
+        ctx.mark_non_differentiable(running_mean, running_var)
+        return y, running_mean, running_var
+
+    @staticmethod
+    def backward(ctx, dy, *_):
+        x, mean, rstd, g32, b32 = ctx.saved_tensors
+        training, act, gdt, bdt = ctx.cfg
+        dx, dgamma, dbeta = bn_act_bwd(dy, x, g32, b32, mean, rstd, training, act)
+        return dx, dgamma.to(gdt), dbeta.to(bdt), None, None, None, None, None, None
 
 
 # =========================================================================================

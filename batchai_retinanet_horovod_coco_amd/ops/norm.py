@@ -1,10 +1,16 @@
-"""GroupNorm + ReLU of the head towers (``--head-norm gn``).
+"""GroupNorm + ReLU of the head towers (``--head-norm gn``), and BatchNorm + activation of the MobileNet backbone.
 
 Statistics are per (image, pyramid level, group) over the level's pixels and the group's channels -- exactly
 ``F.group_norm`` on the level's own ``[B, C, h, w]`` tensor; gamma and beta are shared by the levels like the conv
 weights.  :func:`group_norm_relu_packed` is the torch expression on the packed ``[B, P, C]`` pyramid: the CPU path,
 the fallback for what ``csrc/kernels/group_norm.hip`` does not serve and, in float64, the oracle of its tests.
 :func:`group_norm_relu` dispatches to the fused kernels (``native.GroupNormReluPackedFn``) on the GPU.
+
+BatchNorm + none / ReLU / ReLU6 on NHWC activations: batch statistics per channel over all pixels of the batch in
+training (running statistics updated in place, as ``nn.BatchNorm2d`` does), running statistics in inference.
+:func:`batch_norm_act_torch` is the torch expression -- ``F.batch_norm`` on the NCHW view, then the activation: the
+CPU path, the fallback for what ``csrc/kernels/batch_norm.hip`` does not serve and, in float64, the oracle of its
+tests.  :func:`batch_norm_act` dispatches to the kernels (``native.BatchNormActFn``) on the GPU.
 """
 from __future__ import annotations
 
@@ -61,3 +67,66 @@ def group_norm_relu(x: torch.Tensor, shapes: Sequence[Tuple[int, int]], gamma: t
                 warnings.warn("group_norm.hip does not serve C = {}, {} groups, {} levels, {}: GroupNorm + ReLU runs as "
                               "the torch expression per level".format(*key))
     return group_norm_relu_packed(x, shapes, gamma, beta, groups, eps)
+
+
+def _bn_tensors(bn, momentum, eps):
+    """(gamma, beta, running_mean, running_var, momentum, eps) of a batch-norm module or of such a 4-tuple."""
+    if isinstance(bn, torch.nn.modules.batchnorm._BatchNorm):
+        return bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps
+    gamma, beta, running_mean, running_var = bn
+    return gamma, beta, running_mean, running_var, momentum, eps
+
+
+def batch_norm_act_torch(x: torch.Tensor, bn, training: bool, act: str = "relu6", momentum: float = 0.01,
+                         eps: float = 1e-3) -> torch.Tensor:
+    """The torch expression: ``x`` NHWC, ``bn`` a batch-norm module or ``(gamma, beta, running_mean, running_var)``
+    (then ``momentum`` and ``eps`` apply); returns NHWC (a view of the NCHW result).  In training the running
+    statistics are updated in place."""
+    if act not in ("none", "relu", "relu6"):
+        raise ValueError("batch_norm_act: act 'none', 'relu' or 'relu6' expected, got {!r}".format(act))
+    gamma, beta, rmean, rvar, momentum, eps = _bn_tensors(bn, momentum, eps)
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        gamma, beta = gamma.to(x.dtype), beta.to(x.dtype)
+    y = F.batch_norm(x.permute(0, 3, 1, 2), rmean, rvar, gamma, beta, bool(training), momentum, eps)
+    if act != "none":
+        y = F.relu6(y) if act == "relu6" else F.relu(y)
+    return y.permute(0, 2, 3, 1)
+
+
+def bn_takes_native(x: torch.Tensor, training: bool, backend: str = "auto") -> bool:
+    """Whether :func:`batch_norm_act` would run the kernels on this NHWC input."""
+    if backend == "torch":
+        return False
+    from . import native
+    return x.is_cuda and native.available() and native.bn_served(x, training)
+
+
+def batch_norm_act(x: torch.Tensor, bn, training: bool, act: str = "relu6", backend: str = "auto",
+                   momentum: float = 0.01, eps: float = 1e-3) -> torch.Tensor:
+    """HIP BatchNorm + activation on NHWC ``x`` on the GPU, the torch expression on the CPU.
+
+    ``backend="torch"`` forces the torch expression; ``backend="native"`` raises where the kernels do not serve."""
+    if backend not in ("auto", "native", "torch"):
+        raise ValueError("batch_norm_act: backend 'auto', 'native' or 'torch' expected, got {!r}".format(backend))
+    if act not in ("none", "relu", "relu6"):
+        raise ValueError("batch_norm_act: act 'none', 'relu' or 'relu6' expected, got {!r}".format(act))
+    if backend != "torch":
+        from . import native
+        if x.is_cuda and native.available():
+            gamma, beta, rmean, rvar, mom, ep = _bn_tensors(bn, momentum, eps)
+            try:
+                # NotServed is raised before a kernel runs: the running statistics are still untouched
+                out = native.BatchNormActFn.apply(x, gamma, beta, rmean, rvar, bool(training), float(mom), float(ep), act)
+                return out[0] if training else out
+            except native.NotServed:
+                if backend == "native":
+                    raise
+                key = (int(x.shape[-1]), bool(training), x.dtype)
+                if key not in _FALLBACK_WARNED:
+                    # once per form: a production layer on F.batch_norm + activation should be noticed
+                    _FALLBACK_WARNED.add(key)
+                    warnings.warn("batch_norm.hip does not serve C = {}, training {}, {}: the batch norm runs as the "
+                                  "torch expression".format(*key))
+        elif backend == "native":
+            raise RuntimeError("batch_norm_act: backend 'native' needs a GPU tensor and the HIP kernel library")
+    return batch_norm_act_torch(x, bn, training, act, momentum, eps)
