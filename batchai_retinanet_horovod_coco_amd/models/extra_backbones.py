@@ -17,7 +17,9 @@ As in keras.applications, BN in MobileNet/DenseNet is ordinary (trainable, batch
 training).  VGG convs run through the same conv front-end as ResNet (HIP implicit GEMM when the
 shape class is covered).  MobileNet's 13 depthwise 3x3 convs run on the HIP kernels of ``csrc/kernels/dwconv.hip``
 (``ops.depthwise``) and its 27 batch-norms + ReLU6 on those of ``csrc/kernels/batch_norm.hip`` (``ops.norm``) for bf16
-activations on the GPU; its 1x1 convs and stem and all of DenseNet (which concatenates in NCHW) use PyTorch/MIOpen ops.
+activations on the GPU; its 13 pointwise 1x1 convs run on the MFMA kernels of ``csrc/kernels/pwconv.hip``
+(``ops.pointwise``) when ``pw_backend`` is set to ``auto`` or ``native`` and as PyTorch/MIOpen ops by default; its stem
+(3x3 / s2 on 3 channels) and all of DenseNet (which concatenates in NCHW) use PyTorch/MIOpen ops.
 """
 from __future__ import annotations
 
@@ -29,6 +31,7 @@ import torch.nn.functional as F
 
 from ..ops import depthwise as dw_ops
 from ..ops import norm as norm_ops
+from ..ops import pointwise as pw_ops
 from .layers import Conv2D
 
 
@@ -169,6 +172,10 @@ class MobileNet(nn.Module, _ShapeProbe):
         # 'auto' are profiles/batchnorm.txt)
         self.bn_backend = "auto"
         self.bn_taken = []
+        # the same three for pwconv.hip and the 13 conv_pw layers (profiles/pwconv.txt), but 'torch' by default: the
+        # kernels are opt-in ('auto' or 'native'), see the README
+        self.pw_backend = "torch"
+        self.pw_taken = []
 
     def _depthwise(self, i, x):
         """conv_dw_{i+1} on NCHW ``x``: the kernels on its NHWC view (no pad, no copy once ``x`` is channels-last), or
@@ -182,9 +189,20 @@ class MobileNet(nn.Module, _ShapeProbe):
         x = F.pad(x, (1, 1, 1, 1)) if s == 1 else F.pad(x, (0, 1, 0, 1))
         return self.dw[i](x)
 
+    def _pointwise(self, i, x):
+        """conv_pw_{i+1} on NCHW ``x``: the kernels on its NHWC view (no copy once ``x`` is channels-last), or the torch
+        module; ``self.pw[i]`` stays the holder of the parameter."""
+        xh = x.permute(0, 2, 3, 1)
+        w = self.pw[i].weight
+        if self.pw_backend == "native" or pw_ops.takes_native(xh, w.shape[0], self.pw_backend):
+            self.pw_taken.append("native")
+            return _nchw(pw_ops.pointwise_conv(xh, w, self.pw_backend))
+        self.pw_taken.append("torch")
+        return self.pw[i](x)
+
     def forward(self, x):
         dt = x.dtype
-        self.dw_taken, self.bn_taken = [], []
+        self.dw_taken, self.bn_taken, self.pw_taken = [], [], []
         bn = (self.bn_backend, self.bn_taken)
         with _autocast(x):
             x = _nchw(x)
@@ -201,7 +219,7 @@ class MobileNet(nn.Module, _ShapeProbe):
             outs = []
             for i in range(13):
                 x = self.dw_bn[i](self._depthwise(i, x), *bn)
-                x = self.pw_bn[i](self.pw[i](x), *bn)
+                x = self.pw_bn[i](self._pointwise(i, x), *bn)
                 if i + 1 in (5, 11, 13):
                     outs.append(_nhwc(x).to(dt))
         return outs

@@ -182,6 +182,10 @@ _SIGS = {
     "mxr_dwconv3x3_dgrad": [c_vp] * 3 + [c_int] * 10 + [c_vp],
     "mxr_dwconv_wgrad_work": [c_int] * 4,
     "mxr_dwconv3x3_wgrad": [c_vp] * 4 + [c_ll] + [c_int] * 10 + [c_vp],
+    "mxr_pwconv_fwd": [c_vp] * 3 + [c_ll, c_int, c_int, c_int, c_vp],
+    "mxr_pwconv_dgrad": [c_vp] * 4 + [c_ll, c_int, c_int, c_int, c_vp],
+    "mxr_pwconv_wgrad_work": [c_ll, c_int, c_int],
+    "mxr_pwconv_wgrad": [c_vp] * 4 + [c_ll, c_ll, c_int, c_int, c_int, c_vp],
     "mxr_bn_chunk_rows": [c_int],
     "mxr_bn_work": [c_ll, c_int],
     "mxr_bn_stats": [c_vp] * 6 + [c_ll, c_ll, c_int, c_float, c_float, c_int, c_int, c_vp],
@@ -831,6 +835,108 @@ class DepthwiseConv3x3Fn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dw = dwconv3x3_wgrad(dy, x, stride).t().reshape(x.shape[3], 1, 3, 3).to(wdt)
         return dx, dw, None
+
+
+# =========================================================================================
+# pointwise (1x1) convolution on NHWC bf16 (pwconv.hip)
+# =========================================================================================
+PW_MAX_CHANNELS = 16384
+# (Ci, Co) that 'auto' leaves to the torch form: forward + data gradient + weight gradient lost to it beyond the spread
+# of the rounds (profiles/pwconv.txt: conv_pw_5 of MobileNet-1.0, 0.80x).  'native' still runs them.
+PW_AUTO_EXCLUDED = frozenset({(256, 256)})
+
+
+def pwconv_served(x: torch.Tensor, co: int, auto: bool = False) -> bool:
+    """What ``pwconv.hip`` serves: bf16 ``[..., Ci]`` on the GPU (``M`` = the product of the leading dimensions, below
+    2^31), ``Ci`` and ``co`` multiples of 8 from 8 to 16384 (the entry points' own rule, mirrored so that a caller can
+    decide before allocating).  ``auto``: the answer for the ``auto`` backend, which is ``False`` for every pair in ``PW_AUTO_EXCLUDED``."""
+    ci = int(x.shape[-1]) if x.dim() >= 2 else 0
+    if auto and (ci, int(co)) in PW_AUTO_EXCLUDED:
+        return False
+    return (x.is_cuda and x.dtype == torch.bfloat16 and 8 <= ci <= PW_MAX_CHANNELS and ci % 8 == 0
+            and 8 <= int(co) <= PW_MAX_CHANNELS and int(co) % 8 == 0 and 1 <= x.numel() // ci < 2 ** 31
+            and (not x.is_contiguous() or x.data_ptr() % 16 == 0))
+
+
+def pwconv_weight(weight: torch.Tensor) -> torch.Tensor:
+    """The bf16 ``[Co, Ci]`` matrix of a ``(Co, Ci, 1, 1)`` parameter."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (1, 1):
+        raise ValueError("pointwise conv: a (Co, Ci, 1, 1) weight expected, got {}".format(tuple(weight.shape)))
+    return weight.detach().reshape(weight.shape[0], weight.shape[1]).to(torch.bfloat16).contiguous()
+
+
+def _pw_call(name, fn, *args):
+    rc = fn(*args)
+    if rc == -1:
+        raise NotServed(name)
+    _chk(rc, name)
+
+
+def pwconv_fwd(x, w2):
+    """``y`` bf16 ``[..., Co]`` of ``x`` ``[..., Ci]`` and the bf16 ``[Co, Ci]`` weight; raises :class:`NotServed`."""
+    if w2.dim() != 2 or not pwconv_served(x, w2.shape[0]) or w2.shape[1] != x.shape[-1] or w2.dtype != x.dtype:
+        raise NotServed("pwconv_fwd")       # decided before anything is allocated (the entry point judges again)
+    x, w2 = x.contiguous(), w2.contiguous()
+    co, ci = w2.shape
+    y = torch.empty(tuple(x.shape[:-1]) + (co,), dtype=x.dtype, device=x.device)
+    _pw_call("pwconv_fwd", lib().mxr_pwconv_fwd, _p(x), _p(w2), _p(y), x.numel() // ci, ci, co, _dw_dt(x), _s())
+    return y
+
+
+def pwconv_dgrad(dy, w2):
+    """``dx`` bf16 ``[..., Ci]`` (every element written once) of ``dy`` ``[..., Co]``: the forward kernel on a
+    ``[Ci, Co]`` copy of the weight that the entry point makes in a scratch buffer."""
+    if w2.dim() != 2 or not pwconv_served(dy, w2.shape[1]) or w2.shape[0] != dy.shape[-1] or w2.dtype != dy.dtype:
+        raise NotServed("pwconv_dgrad")
+    dy, w2 = dy.contiguous(), w2.contiguous()
+    co, ci = w2.shape
+    dx = torch.empty(tuple(dy.shape[:-1]) + (ci,), dtype=dy.dtype, device=dy.device)
+    wt = torch.empty((ci, co), dtype=w2.dtype, device=dy.device)
+    _pw_call("pwconv_dgrad", lib().mxr_pwconv_dgrad, _p(dy), _p(w2), _p(wt), _p(dx), dy.numel() // co, ci, co,
+             _dw_dt(dy), _s())
+    return dx
+
+
+def pwconv_wgrad(dy, x):
+    """``dw`` fp32 ``[Co, Ci]``: the sum over the ``M`` rows of ``dy[m, co] * x[m, ci]``, in a fixed order."""
+    co = int(dy.shape[-1]) if dy.dim() >= 2 else 0
+    if not pwconv_served(x, co) or not pwconv_served(dy, x.shape[-1]) or dy.shape[:-1] != x.shape[:-1]:
+        raise NotServed("pwconv_wgrad")
+    dy, x = dy.contiguous(), x.contiguous()
+    ci = int(x.shape[-1])
+    m = x.numel() // ci
+    nwork = lib().mxr_pwconv_wgrad_work(m, ci, co)
+    if nwork <= 0:
+        raise NotServed("pwconv_wgrad")
+    dw = torch.empty((co, ci), dtype=torch.float32, device=x.device)
+    work = torch.empty(nwork, dtype=torch.float32, device=x.device)
+    _pw_call("pwconv_wgrad", lib().mxr_pwconv_wgrad, _p(dy), _p(x), _p(dw), _p(work), nwork, m, ci, co, _dw_dt(x), _s())
+    return dw
+
+
+class PointwiseConvFn(torch.autograd.Function):
+    """1x1 conv of NHWC bf16 ``x`` with a ``(Co, Ci, 1, 1)`` weight; saves x and the bf16 weight matrix."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        if weight.dim() != 4 or not pwconv_served(x, weight.shape[0]):
+            raise NotServed("pwconv_fwd")       # before the bf16 copy of the weight exists
+        x = x.contiguous()
+        w2 = pwconv_weight(weight)
+        y = pwconv_fwd(x, w2)
+        ctx.save_for_backward(x, w2)
+        ctx.wdt = weight.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w2 = ctx.saved_tensors
+        dy = dy.to(x.dtype)
+        dx = pwconv_dgrad(dy, w2) if ctx.needs_input_grad[0] else None
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dw = pwconv_wgrad(dy, x).reshape(w2.shape[0], w2.shape[1], 1, 1).to(ctx.wdt)
+        return dx, dw
 
 
 # =========================================================================================
