@@ -19,7 +19,10 @@ shape class is covered).  MobileNet's 13 depthwise 3x3 convs run on the HIP kern
 (``ops.depthwise``) and its 27 batch-norms + ReLU6 on those of ``csrc/kernels/batch_norm.hip`` (``ops.norm``) for bf16
 activations on the GPU; its 13 pointwise 1x1 convs run on the MFMA kernels of ``csrc/kernels/pwconv.hip``
 (``ops.pointwise``) when ``pw_backend`` is set to ``auto`` or ``native`` and as PyTorch/MIOpen ops by default; its stem
-(3x3 / s2 on 3 channels) and all of DenseNet (which concatenates in NCHW) use PyTorch/MIOpen ops.
+(3x3 / s2 on 3 channels) runs on the MFMA kernels of ``csrc/kernels/stem3x3.hip`` (``ops.stem3x3``), straight from the
+NHWC image with the padding inside the kernel, when ``stem_backend`` is set to ``auto`` or ``native`` and as pad +
+PyTorch/MIOpen conv + channels-last copy by default.  All of DenseNet (which concatenates in NCHW) uses PyTorch/MIOpen
+ops.
 """
 from __future__ import annotations
 
@@ -32,6 +35,7 @@ import torch.nn.functional as F
 from ..ops import depthwise as dw_ops
 from ..ops import norm as norm_ops
 from ..ops import pointwise as pw_ops
+from ..ops import stem3x3 as stem_ops
 from .layers import Conv2D
 
 
@@ -176,6 +180,10 @@ class MobileNet(nn.Module, _ShapeProbe):
         # kernels are opt-in ('auto' or 'native'), see the README
         self.pw_backend = "torch"
         self.pw_taken = []
+        # the same three for stem3x3.hip and conv1 (profiles/stem3x3.txt), 'torch' by default as well; the path of the
+        # last forward: 'native' or 'torch'
+        self.stem_backend = "torch"
+        self.stem_taken = None
 
     def _depthwise(self, i, x):
         """conv_dw_{i+1} on NCHW ``x``: the kernels on its NHWC view (no pad, no copy once ``x`` is channels-last), or
@@ -200,14 +208,26 @@ class MobileNet(nn.Module, _ShapeProbe):
         self.pw_taken.append("torch")
         return self.pw[i](x)
 
+    def _stem(self, x):
+        """conv1 on the NHWC image, NCHW out: the kernels (padding inside, NHWC result, so the view returned is already
+        channels-last), or pad + the torch module; ``self.conv1`` stays the holder of the parameter."""
+        if self.stem_backend not in ("auto", "native", "torch"):
+            raise ValueError("MobileNet.stem_backend: 'auto', 'native' or 'torch' expected, got {!r}".format(
+                self.stem_backend))
+        w = self.conv1.weight
+        if self.stem_backend == "native" or stem_ops.takes_native(x, w.shape[0], self.stem_backend):
+            self.stem_taken = "native"
+            return _nchw(stem_ops.stem_conv3x3(x, w, self.stem_backend))
+        self.stem_taken = "torch"
+        x = F.pad(_nchw(x), (0, 1, 0, 1))                # keras: ZeroPadding2D(((0,1),(0,1))) + valid s2
+        return self.conv1(x)
+
     def forward(self, x):
         dt = x.dtype
         self.dw_taken, self.bn_taken, self.pw_taken = [], [], []
         bn = (self.bn_backend, self.bn_taken)
         with _autocast(x):
-            x = _nchw(x)
-            x = F.pad(x, (0, 1, 0, 1))                   # keras: ZeroPadding2D(((0,1),(0,1))) + valid s2
-            x = self.conv1(x)
+            x = self._stem(x)
             xh = x.permute(0, 2, 3, 1)
             if self.bn_backend == "native" or norm_ops.bn_takes_native(xh, self.training, self.bn_backend):
                 # once, in front of the first norm: all 27 are served on NHWC views that are no copies

@@ -186,6 +186,10 @@ _SIGS = {
     "mxr_pwconv_dgrad": [c_vp] * 4 + [c_ll, c_int, c_int, c_int, c_vp],
     "mxr_pwconv_wgrad_work": [c_ll, c_int, c_int],
     "mxr_pwconv_wgrad": [c_vp] * 4 + [c_ll, c_ll, c_int, c_int, c_int, c_vp],
+    "mxr_stem3_pack": [c_vp, c_int, c_vp, c_int, c_vp],
+    "mxr_stem3_fwd": [c_vp] * 3 + [c_ll, c_ll, c_ll, c_int, c_int, c_int, c_vp],
+    "mxr_stem3_wgrad_work": [c_ll, c_ll, c_ll, c_int],
+    "mxr_stem3_wgrad": [c_vp] * 4 + [c_ll, c_ll, c_ll, c_ll, c_int, c_int, c_vp],
     "mxr_bn_chunk_rows": [c_int],
     "mxr_bn_work": [c_ll, c_int],
     "mxr_bn_stats": [c_vp] * 6 + [c_ll, c_ll, c_int, c_float, c_float, c_int, c_int, c_vp],
@@ -937,6 +941,94 @@ class PointwiseConvFn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dw = pwconv_wgrad(dy, x).reshape(w2.shape[0], w2.shape[1], 1, 1).to(ctx.wdt)
         return dx, dw
+
+
+# =========================================================================================
+# MobileNet's stem: 3x3 / s2 convolution of the 3-channel NHWC bf16 image (stem3x3.hip)
+# =========================================================================================
+# Co that 'auto' leaves to the torch form: forward + weight gradient lost to it in profiles/stem3x3.txt.  'native'
+# still runs them.
+STEM3_AUTO_EXCLUDED = frozenset()
+
+
+def stem3_served(x: torch.Tensor, co: int, auto: bool = False) -> bool:
+    """What ``stem3x3.hip`` serves: a bf16 ``[N, H, W, 3]`` image on the GPU that needs no gradient, ``H, W >= 2``,
+    ``co`` in 8, 16, 24, 32, ``N * H * W * 3`` and ``N * Ho * Wo * 32`` below 2^31 (the entry points' own rule,
+    mirrored so that a caller can decide before allocating).  The image needs 2-byte alignment only: a view at an odd
+    element offset is served.  ``auto``: the answer for the ``auto`` backend, ``False`` for ``STEM3_AUTO_EXCLUDED``."""
+    co = int(co)
+    if auto and co in STEM3_AUTO_EXCLUDED:
+        return False
+    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16 and x.shape[3] == 3 and not x.requires_grad
+            and x.shape[0] >= 1 and x.shape[1] >= 2 and x.shape[2] >= 2 and co in (8, 16, 24, 32)):
+        return False
+    _, _, Ho, Wo = dwconv_geometry(x.shape[1], x.shape[2], 2)
+    return x.numel() < 2 ** 31 and x.shape[0] * Ho * Wo * 32 < 2 ** 31
+
+
+def stem3_weight(weight: torch.Tensor) -> torch.Tensor:
+    """The packed bf16 ``[32][32]`` image of a ``(Co, 3, 3, 3)`` fp32 or bf16 parameter (rows in the forward's MFMA row
+    order, columns in the kernels' k-slot order; one small launch)."""
+    if weight.dim() != 4 or tuple(weight.shape[1:]) != (3, 3, 3):
+        raise ValueError("stem 3x3: a (Co, 3, 3, 3) weight expected, got {}".format(tuple(weight.shape)))
+    w = weight.detach().contiguous()
+    if not w.is_cuda or w.dtype not in (torch.float32, torch.bfloat16):
+        raise NotServed("stem3_weight")
+    wpk = torch.empty((32, 32), dtype=torch.bfloat16, device=w.device)
+    _pw_call("stem3_weight", lib().mxr_stem3_pack, _p(w), _dw_dt(w), _p(wpk), int(w.shape[0]), _s())
+    return wpk
+
+
+def stem3_fwd(x, wpk, co):
+    """``y`` bf16 ``[N, Ho, Wo, co]`` of the NHWC image and :func:`stem3_weight`'s image; raises :class:`NotServed`."""
+    if not stem3_served(x, co) or tuple(wpk.shape) != (32, 32) or wpk.dtype != x.dtype:
+        raise NotServed("stem3_fwd")        # decided before anything is allocated (the entry point judges again)
+    x = x.contiguous()
+    N, H, W, _ = x.shape
+    _, _, Ho, Wo = dwconv_geometry(H, W, 2)
+    y = torch.empty((N, Ho, Wo, int(co)), dtype=x.dtype, device=x.device)
+    _pw_call("stem3_fwd", lib().mxr_stem3_fwd, _p(x), _p(wpk), _p(y), N, H, W, int(co), _dw_dt(x), 0, _s())
+    return y
+
+
+def stem3_wgrad(dy, x):
+    """``dw`` fp32 ``(Co, 3, 3, 3)``: the sum over the ``N * Ho * Wo`` pixels of ``dy * patch``, in a fixed order."""
+    co = int(dy.shape[-1]) if dy.dim() == 4 else 0
+    if not stem3_served(x, co) or not dy.is_cuda or dy.dtype != x.dtype:
+        raise NotServed("stem3_wgrad")
+    x, dy = x.contiguous(), dy.contiguous()
+    N, H, W, _ = x.shape
+    _, _, Ho, Wo = dwconv_geometry(H, W, 2)
+    if tuple(dy.shape) != (N, Ho, Wo, co):
+        raise ValueError("stem3_wgrad: dy {} does not match x {}".format(tuple(dy.shape), tuple(x.shape)))
+    nwork = lib().mxr_stem3_wgrad_work(N, Ho, Wo, co)
+    if nwork <= 0:
+        raise NotServed("stem3_wgrad")
+    dw = torch.empty((co, 3, 3, 3), dtype=torch.float32, device=x.device)
+    work = torch.empty(nwork, dtype=torch.float32, device=x.device)
+    _pw_call("stem3_wgrad", lib().mxr_stem3_wgrad, _p(dy), _p(x), _p(dw), _p(work), nwork, N, H, W, co, _dw_dt(x), _s())
+    return dw
+
+
+class Stem3x3Fn(torch.autograd.Function):
+    """3x3 / s2 conv of the NHWC bf16 image with a ``(Co, 3, 3, 3)`` weight; saves the image only.  There is no data
+    gradient: an image that requires one is refused, never answered with ``None``."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        if ctx.needs_input_grad[0] or weight.dim() != 4 or not stem3_served(x, weight.shape[0]):
+            raise NotServed("stem3_fwd")        # before the packed weight exists
+        x = x.contiguous()
+        y = stem3_fwd(x, stem3_weight(weight), weight.shape[0])
+        ctx.save_for_backward(x)
+        ctx.wdt = weight.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        dw = stem3_wgrad(dy.to(x.dtype), x).to(ctx.wdt) if ctx.needs_input_grad[1] else None
+        return None, dw
 
 
 # =========================================================================================
