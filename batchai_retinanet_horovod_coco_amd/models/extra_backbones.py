@@ -21,7 +21,9 @@ activations on the GPU; its 13 pointwise 1x1 convs run on the MFMA kernels of ``
 (``ops.pointwise``) when ``pw_backend`` is set to ``auto`` or ``native`` and as PyTorch/MIOpen ops by default; its stem
 (3x3 / s2 on 3 channels) runs on the MFMA kernels of ``csrc/kernels/stem3x3.hip`` (``ops.stem3x3``), straight from the
 NHWC image with the padding inside the kernel, when ``stem_backend`` is set to ``auto`` or ``native`` and as pad +
-PyTorch/MIOpen conv + channels-last copy by default.  All of DenseNet (which concatenates in NCHW) uses PyTorch/MIOpen
+PyTorch/MIOpen conv + channels-last copy by default.  When the model is not training and ``block_backend`` is set to
+``auto`` or ``native``, each of the 13 blocks (depthwise conv, norm, pointwise conv, norm) runs as one launch of
+``csrc/kernels/sepblock.hip`` (``ops.separable``) instead of its four layers.  All of DenseNet (which concatenates in NCHW) uses PyTorch/MIOpen
 ops.
 """
 from __future__ import annotations
@@ -35,6 +37,7 @@ import torch.nn.functional as F
 from ..ops import depthwise as dw_ops
 from ..ops import norm as norm_ops
 from ..ops import pointwise as pw_ops
+from ..ops import separable as sep_ops
 from ..ops import stem3x3 as stem_ops
 from .layers import Conv2D
 
@@ -184,6 +187,25 @@ class MobileNet(nn.Module, _ShapeProbe):
         # last forward: 'native' or 'torch'
         self.stem_backend = "torch"
         self.stem_taken = None
+        # the same three for sepblock.hip, which runs a whole block (conv_dw, its norm, conv_pw, its norm) as one launch
+        # when the model is not training (profiles/sepblock.txt); 'torch' by default: the four layers.  Per block of
+        # the last forward: 'fused' or 'layers'
+        self.block_backend = "torch"
+        self.block_taken = []
+
+    def _block(self, i, x):
+        """Block ``i + 1`` on NCHW ``x`` in one launch (eval mode only), or ``None`` where the four layers are to run;
+        the modules stay the holders of every parameter and buffer."""
+        if self.block_backend not in ("auto", "native", "torch"):
+            raise ValueError("MobileNet.block_backend: 'auto', 'native' or 'torch' expected, got {!r}".format(
+                self.block_backend))
+        if self.training or self.block_backend == "torch":
+            return None
+        xh = x.permute(0, 2, 3, 1)
+        ops = (xh, self.dw[i].weight, self.dw_bn[i].bn, self.pw[i].weight, self.pw_bn[i].bn, self.strides[i])
+        if self.block_backend == "native" or sep_ops.takes_native(*ops, self.block_backend):
+            return _nchw(sep_ops.separable_block_eval(*ops, self.block_backend))
+        return None
 
     def _depthwise(self, i, x):
         """conv_dw_{i+1} on NCHW ``x``: the kernels on its NHWC view (no pad, no copy once ``x`` is channels-last), or
@@ -224,7 +246,7 @@ class MobileNet(nn.Module, _ShapeProbe):
 
     def forward(self, x):
         dt = x.dtype
-        self.dw_taken, self.bn_taken, self.pw_taken = [], [], []
+        self.dw_taken, self.bn_taken, self.pw_taken, self.block_taken = [], [], [], []
         bn = (self.bn_backend, self.bn_taken)
         with _autocast(x):
             x = self._stem(x)
@@ -238,8 +260,13 @@ class MobileNet(nn.Module, _ShapeProbe):
                 x = x.contiguous(memory_format=torch.channels_last)
             outs = []
             for i in range(13):
-                x = self.dw_bn[i](self._depthwise(i, x), *bn)
-                x = self.pw_bn[i](self._pointwise(i, x), *bn)
+                y = self._block(i, x)
+                self.block_taken.append("layers" if y is None else "fused")
+                if y is None:
+                    x = self.dw_bn[i](self._depthwise(i, x), *bn)
+                    x = self.pw_bn[i](self._pointwise(i, x), *bn)
+                else:
+                    x = y
                 if i + 1 in (5, 11, 13):
                     outs.append(_nhwc(x).to(dt))
         return outs

@@ -186,6 +186,8 @@ _SIGS = {
     "mxr_pwconv_dgrad": [c_vp] * 4 + [c_ll, c_int, c_int, c_int, c_vp],
     "mxr_pwconv_wgrad_work": [c_ll, c_int, c_int],
     "mxr_pwconv_wgrad": [c_vp] * 4 + [c_ll, c_ll, c_int, c_int, c_int, c_vp],
+    "mxr_sepblock_geometry": [c_int, c_vp],
+    "mxr_sepblock_fwd": [c_vp] * 6 + [c_float] + [c_vp] * 5 + [c_float, c_vp] + [c_int] * 11 + [c_vp],
     "mxr_stem3_pack": [c_vp, c_int, c_vp, c_int, c_vp],
     "mxr_stem3_fwd": [c_vp] * 3 + [c_ll, c_ll, c_ll, c_int, c_int, c_int, c_vp],
     "mxr_stem3_wgrad_work": [c_ll, c_ll, c_ll, c_int],
@@ -941,6 +943,63 @@ class PointwiseConvFn(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dw = pwconv_wgrad(dy, x).reshape(w2.shape[0], w2.shape[1], 1, 1).to(ctx.wdt)
         return dx, dw
+
+
+# =========================================================================================
+# a whole depthwise-separable block in eval mode, one launch (sepblock.hip)
+# =========================================================================================
+SEP_MAX_CHANNELS = 1024
+# (Ci, Co, stride) that 'auto' leaves to the per-layer path: the fused kernel lost to the better of the per-layer native
+# chain and the torch form beyond the spread of the rounds (profiles/sepblock.txt: blocks 7 to 13 of MobileNet-1.0, the
+# 64-pixel tile form, 0.64x, 0.44x and 0.33x of the per-layer native chain).  'native' still runs them.
+SEP_AUTO_EXCLUDED = frozenset({(512, 512, 1), (512, 1024, 2), (1024, 1024, 1)})
+
+
+def sepblock_served(x: torch.Tensor, ci: int, co: int, stride: int, auto: bool = False) -> bool:
+    """What ``sepblock.hip`` serves: bf16 ``[N, H, W, ci]`` on the GPU, ``ci`` and ``co`` multiples of 8 from 8 to 1024,
+    stride 1 or 2 (stride 2 on at least 2 x 2 pixels), ``1 <= N <= 65535`` (the entry point's own rule, mirrored so that
+    a caller can decide before allocating).  ``auto``: the answer for the ``auto`` backend, ``False`` for every form in
+    ``SEP_AUTO_EXCLUDED``."""
+    ci, co = int(ci), int(co)
+    if auto and (ci, co, int(stride)) in SEP_AUTO_EXCLUDED:
+        return False
+    return (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16 and x.shape[3] == ci
+            and 8 <= ci <= SEP_MAX_CHANNELS and ci % 8 == 0 and 8 <= co <= SEP_MAX_CHANNELS and co % 8 == 0
+            and 1 <= x.shape[0] <= 65535 and x.shape[1] <= 2 ** 24 and x.shape[2] <= 2 ** 24
+            and (stride == 1 or (stride == 2 and x.shape[1] >= 2 and x.shape[2] >= 2))
+            and (not x.is_contiguous() or x.data_ptr() % 16 == 0))
+
+
+def sepblock_geometry(ci: int):
+    """(pixels of a workgroup's tile, its columns, k of a weight stage, rows of a depthwise item, LDS bytes) of
+    ``sepblock.hip`` for ``ci`` input channels."""
+    out = (c_int * 5)()
+    if lib().mxr_sepblock_geometry(int(ci), ctypes.addressof(out)) != 0:
+        raise NotServed("sepblock_geometry")
+    return tuple(out)
+
+
+def sepblock_fwd(x, w9, bn1, w2, bn2, stride):
+    """``y`` bf16 ``[N, Ho, Wo, Co]`` of one depthwise-separable block in eval mode, one launch: NHWC ``x``, the
+    ``[9][Ci]`` fp32 taps, the bf16 ``[Co, Ci]`` matrix and, per norm, ``(gamma, beta, running_mean, running_var, eps)``
+    with fp32 vectors, folded inside the kernel.  Raises :class:`NotServed`."""
+    co = int(w2.shape[0]) if w2.dim() == 2 else 0
+    ci = int(x.shape[3]) if x.dim() == 4 else 0
+    vecs = [v.detach() for v in tuple(bn1[:4]) + tuple(bn2[:4])]
+    if (not sepblock_served(x, ci, co, stride) or tuple(w9.shape) != (9, ci) or w9.dtype != torch.float32
+            or tuple(w2.shape) != (co, ci) or w2.dtype != torch.bfloat16
+            or any(v.dtype != torch.float32 or v.device != x.device for v in vecs)
+            or any(v.numel() != ci for v in vecs[:4]) or any(v.numel() != co for v in vecs[4:])):
+        raise NotServed("sepblock_fwd")     # decided before anything is allocated (the entry point judges again)
+    x, w9, w2 = x.contiguous(), w9.contiguous(), w2.contiguous()
+    vecs = [v.contiguous() for v in vecs]
+    N, H, W, _ = x.shape
+    pt, pl, Ho, Wo = dwconv_geometry(H, W, stride)
+    y = torch.empty((N, Ho, Wo, co), dtype=x.dtype, device=x.device)
+    _dw_call("sepblock_fwd", lib().mxr_sepblock_fwd, _p(x), _p(w9), *[_p(v) for v in vecs[:4]], float(bn1[4]), _p(w2),
+             *[_p(v) for v in vecs[4:]], float(bn2[4]), _p(y), N, H, W, ci, co, int(stride), pt, pl, Ho, Wo, _dw_dt(x),
+             _s())
+    return y
 
 
 # =========================================================================================
