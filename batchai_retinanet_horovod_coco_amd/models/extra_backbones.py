@@ -23,7 +23,8 @@ activations on the GPU; its 13 pointwise 1x1 convs run on the MFMA kernels of ``
 NHWC image with the padding inside the kernel, when ``stem_backend`` is set to ``auto`` or ``native`` and as pad +
 PyTorch/MIOpen conv + channels-last copy by default.  When the model is not training and ``block_backend`` is set to
 ``auto`` or ``native``, each of the 13 blocks (depthwise conv, norm, pointwise conv, norm) runs as one launch of
-``csrc/kernels/sepblock.hip`` (``ops.separable``) instead of its four layers.  All of DenseNet (which concatenates in NCHW) uses PyTorch/MIOpen
+``csrc/kernels/sepblock.hip`` or, for the wide blocks (``Ci > 256``), of its K-streamed form
+``csrc/kernels/sepblock_stream.hip`` (``ops.separable``) instead of its four layers.  All of DenseNet (which concatenates in NCHW) uses PyTorch/MIOpen
 ops.
 """
 from __future__ import annotations
@@ -188,8 +189,9 @@ class MobileNet(nn.Module, _ShapeProbe):
         self.stem_backend = "torch"
         self.stem_taken = None
         # the same three for sepblock.hip, which runs a whole block (conv_dw, its norm, conv_pw, its norm) as one launch
-        # when the model is not training (profiles/sepblock.txt); 'torch' by default: the four layers.  Per block of
-        # the last forward: 'fused' or 'layers'
+        # when the model is not training (profiles/sepblock.txt; blocks 7 to 13 on sepblock_stream.hip,
+        # profiles/sepblock_stream.txt); 'torch' by default: the four layers.  Per block of the last forward: 'fused'
+        # (either kernel form) or 'layers'
         self.block_backend = "torch"
         self.block_taken = []
 

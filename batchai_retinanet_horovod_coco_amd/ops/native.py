@@ -188,6 +188,7 @@ _SIGS = {
     "mxr_pwconv_wgrad": [c_vp] * 4 + [c_ll, c_ll, c_int, c_int, c_int, c_vp],
     "mxr_sepblock_geometry": [c_int, c_vp],
     "mxr_sepblock_fwd": [c_vp] * 6 + [c_float] + [c_vp] * 5 + [c_float, c_vp] + [c_int] * 11 + [c_vp],
+    "mxr_sepblock_stream_fwd": [c_vp] * 6 + [c_float] + [c_vp] * 5 + [c_float, c_vp] + [c_int] * 11 + [c_vp],
     "mxr_stem3_pack": [c_vp, c_int, c_vp, c_int, c_vp],
     "mxr_stem3_fwd": [c_vp] * 3 + [c_ll, c_ll, c_ll, c_int, c_int, c_int, c_vp],
     "mxr_stem3_wgrad_work": [c_ll, c_ll, c_ll, c_int],
@@ -946,13 +947,16 @@ class PointwiseConvFn(torch.autograd.Function):
 
 
 # =========================================================================================
-# a whole depthwise-separable block in eval mode, one launch (sepblock.hip)
+# a whole depthwise-separable block in eval mode, one launch (sepblock.hip, sepblock_stream.hip)
 # =========================================================================================
 SEP_MAX_CHANNELS = 1024
-# (Ci, Co, stride) that 'auto' leaves to the per-layer path: the fused kernel lost to the better of the per-layer native
-# chain and the torch form beyond the spread of the rounds (profiles/sepblock.txt: blocks 7 to 13 of MobileNet-1.0, the
-# 64-pixel tile form, 0.64x, 0.44x and 0.33x of the per-layer native chain).  'native' still runs them.
-SEP_AUTO_EXCLUDED = frozenset({(512, 512, 1), (512, 1024, 2), (1024, 1024, 1)})
+SEP_STREAM_MIN_CI = 32
+# (Ci, Co, stride) that 'auto' leaves to the per-layer path: the fused form that 'auto' would run (sepblock_form) lost to
+# the better of the per-layer native chain and the torch form beyond the spread of the rounds.  Empty since
+# sepblock_stream.hip: profiles/sepblock_stream.txt lists no losing form (blocks 7 to 11, 12 and 13 of MobileNet-1.0,
+# which the resident form loses at 0.66x, 0.47x and 0.34x of the per-layer native chain, take the stream form at 2.10x,
+# 1.84x and 1.66x).  The mechanism stays for the next measurement; 'native' ignores it.
+SEP_AUTO_EXCLUDED = frozenset()
 
 
 def sepblock_served(x: torch.Tensor, ci: int, co: int, stride: int, auto: bool = False) -> bool:
@@ -979,24 +983,40 @@ def sepblock_geometry(ci: int):
     return tuple(out)
 
 
-def sepblock_fwd(x, w9, bn1, w2, bn2, stride):
+def sepblock_form(ci: int, co: int) -> str:
+    """The kernel form that :func:`sepblock_fwd` picks by default: ``"stream"`` (``sepblock_stream.hip``: ``Ci`` walked
+    in chunks of 32, ``Z`` never resident) iff ``ci > 256 and co >= 256``, where the resident form is down to a 64-pixel
+    tile and re-reads the whole weight per tile; else ``"resident"`` (``sepblock.hip``)."""
+    return "stream" if int(ci) > 256 and int(co) >= 256 else "resident"
+
+
+def sepblock_fwd(x, w9, bn1, w2, bn2, stride, form=None):
     """``y`` bf16 ``[N, Ho, Wo, Co]`` of one depthwise-separable block in eval mode, one launch: NHWC ``x``, the
     ``[9][Ci]`` fp32 taps, the bf16 ``[Co, Ci]`` matrix and, per norm, ``(gamma, beta, running_mean, running_var, eps)``
-    with fp32 vectors, folded inside the kernel.  Raises :class:`NotServed`."""
+    with fp32 vectors, folded inside the kernel.  ``form``: ``"resident"`` (``sepblock.hip``), ``"stream"``
+    (``sepblock_stream.hip``: additionally ``Ci >= 32`` and fewer than ``2^31 - 128`` output pixels) or ``None`` for
+    :func:`sepblock_form`'s choice.  Raises :class:`NotServed`, also where a named form does not serve the shape."""
     co = int(w2.shape[0]) if w2.dim() == 2 else 0
     ci = int(x.shape[3]) if x.dim() == 4 else 0
+    if form is None:
+        form = sepblock_form(ci, co)
+    if form not in ("resident", "stream"):
+        raise ValueError("sepblock_fwd: form 'resident', 'stream' or None expected, got {!r}".format(form))
     vecs = [v.detach() for v in tuple(bn1[:4]) + tuple(bn2[:4])]
     if (not sepblock_served(x, ci, co, stride) or tuple(w9.shape) != (9, ci) or w9.dtype != torch.float32
             or tuple(w2.shape) != (co, ci) or w2.dtype != torch.bfloat16
             or any(v.dtype != torch.float32 or v.device != x.device for v in vecs)
             or any(v.numel() != ci for v in vecs[:4]) or any(v.numel() != co for v in vecs[4:])):
         raise NotServed("sepblock_fwd")     # decided before anything is allocated (the entry point judges again)
-    x, w9, w2 = x.contiguous(), w9.contiguous(), w2.contiguous()
-    vecs = [v.contiguous() for v in vecs]
     N, H, W, _ = x.shape
     pt, pl, Ho, Wo = dwconv_geometry(H, W, stride)
+    if form == "stream" and (ci < SEP_STREAM_MIN_CI or N * Ho * Wo >= 2 ** 31 - 128):
+        raise NotServed("sepblock_fwd")
+    x, w9, w2 = x.contiguous(), w9.contiguous(), w2.contiguous()
+    vecs = [v.contiguous() for v in vecs]
     y = torch.empty((N, Ho, Wo, co), dtype=x.dtype, device=x.device)
-    _dw_call("sepblock_fwd", lib().mxr_sepblock_fwd, _p(x), _p(w9), *[_p(v) for v in vecs[:4]], float(bn1[4]), _p(w2),
+    fn = lib().mxr_sepblock_stream_fwd if form == "stream" else lib().mxr_sepblock_fwd
+    _dw_call("sepblock_fwd", fn, _p(x), _p(w9), *[_p(v) for v in vecs[:4]], float(bn1[4]), _p(w2),
              *[_p(v) for v in vecs[4:]], float(bn2[4]), _p(y), N, H, W, ci, co, int(stride), pt, pl, Ho, Wo, _dw_dt(x),
              _s())
     return y

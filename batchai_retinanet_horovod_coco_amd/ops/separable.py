@@ -7,7 +7,10 @@ window) and both norms on their running statistics.
 
 :func:`separable_block_eval_torch` is the torch expression: the CPU path, the fallback for what
 ``csrc/kernels/sepblock.hip`` does not serve and, in float64, the oracle of its tests.  :func:`separable_block_eval`
-dispatches to the kernel (``native.sepblock_fwd``: the whole block in one launch, forward only) on the GPU.
+dispatches to the kernel (``native.sepblock_fwd``: the whole block in one launch, forward only) on the GPU.  The kernel
+has two forms that compute the same function, and ``native.sepblock_form(Ci, Co)`` picks between them: the resident
+form of ``sepblock.hip`` (``Z`` of a tile in LDS) and, for ``Ci > 256`` with ``Co >= 256``, the K-streamed form of
+``csrc/kernels/sepblock_stream.hip``.  There is no switch for the form here.
 """
 from __future__ import annotations
 

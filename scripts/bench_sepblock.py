@@ -2,13 +2,16 @@
 at batch 16, 800 x 1333, bf16, against the two forms it can replace: the per-layer native chain (dwconv.hip,
 batch_norm.hip, pwconv.hip, batch_norm.hip: ``dw_backend = bn_backend = pw_backend = "native"``) and the torch form
 (all three ``"torch"``), both run through the backbone's own layer methods.  Per distinct block form the three
-alternate within each of ROUNDS rounds of CALLS calls after a warm-up.  Next to each time stands the rate of the bytes
+alternate within each of ROUNDS rounds of CALLS calls after a warm-up.  Where ``native.sepblock_form`` picks the stream
+form (csrc/kernels/sepblock_stream.hip: blocks 7 to 13), both fused forms are timed, and the verdict is about the one
+``auto`` would run.  Next to each time stands the rate of the bytes
 the block must move (x once, y once; weights and vectors are noise), to be read against the 5.0 to 6.0 TB/s of
 profiles/r5_hbm_bw_probe.txt.  A form whose fused time exceeds the better of the other two by more than the spread of
 the rounds is marked LOSES: those are the forms for ``native.SEP_AUTO_EXCLUDED``.  Last, a whole eval forward of
-MobileNet(1.0) is timed with ``block_backend = "native"`` and ``"auto"`` over the native layers, and as the native
+MobileNet(1.0) is timed with ``block_backend = "native"`` and ``"auto"`` over the native layers (``auto`` also with
+this run's losing forms and with every stream form excluded, the forward before the stream kernel), and as the native
 layers and the torch layers alone.
-python scripts/bench_sepblock.py [--batch 16] [--out FILE]"""
+python scripts/bench_sepblock.py [--batch 16] [--out FILE]   (profiles/sepblock.txt, profiles/sepblock_stream.txt)"""
 import argparse
 import os
 import sys
@@ -97,20 +100,30 @@ def main():
                     y = net.dw_bn[i](net._depthwise(i, x), backend)
                     return net.pw_bn[i](net._pointwise(i, y), backend)
 
-            fused = SB.separable_block_eval(*ops, backend="native")
+            def fused_as(form):
+                # what separable_block_eval launches (tap table, bf16 weight, the kernel), with the form named
+                return N.sepblock_fwd(xh, N.dwconv_taps(ops[1]), SB._bn_operands(ops[2]), N.pwconv_weight(ops[3]),
+                                      SB._bn_operands(ops[4]), s, form=form)
+
+            # the form 'auto' would run comes first; where that is the stream form, the resident form is timed as well
+            forms = ["stream", "resident"] if N.sepblock_form(ci, co) == "stream" else ["resident"]
+            fused = fused_as(forms[0])
+            assert torch.equal(fused, SB.separable_block_eval(*ops, backend="native"))
             chain = layers("native").permute(0, 2, 3, 1)
             differ = float((fused.float() - chain.float()).abs().max())
-            res = rounds([lambda: SB.separable_block_eval(*ops, backend="native"), lambda: layers("native"),
-                          lambda: layers("torch")])
+            res = rounds([lambda f=f: fused_as(f) for f in forms] + [lambda: layers("native"), lambda: layers("torch")])
             nbytes = 2 * (xh.numel() + fused.numel())
             P, tw, kc, R, lds = N.sepblock_geometry(ci)
-            lines.append("block {} ({} block{}): {} x {} x {} -> {} x {} x {}, stride {}; tile 8 x {}, weight stage {} k, "
-                         "{:.1f} KB LDS; max |fused - native layers| {:.3f}".format(
+            lines.append("block {} ({} block{}): {} x {} x {} -> {} x {} x {}, stride {}; resident form: tile 8 x {}, "
+                         "weight stage {} k, {:.1f} KB LDS; max |fused ({}) - native layers| {:.3f}".format(
                              ", ".join(str(b + 1) for b in blocks), len(blocks), "s" if len(blocks) > 1 else "", H, W, ci,
-                             fused.shape[1], fused.shape[2], co, s, tw, kc, lds / 1024, differ))
-            for name, (med, lo, hi) in zip(("fused", "native layers", "torch layers"), res):
-                lines.append("  {:<13} {:9.1f} us ({:9.1f} .. {:9.1f})  {:5.2f} TB/s".format(name, med, lo, hi,
-                                                                                          nbytes / med * 1e-6))
+                             fused.shape[1], fused.shape[2], co, s, tw, kc, lds / 1024, forms[0], differ))
+            for name, (med, lo, hi) in zip(["fused " + f for f in forms] + ["native layers", "torch layers"], res):
+                lines.append("  {:<14} {:9.1f} us ({:9.1f} .. {:9.1f})  {:5.2f} TB/s".format(name, med, lo, hi,
+                                                                                           nbytes / med * 1e-6))
+            if len(forms) == 2:
+                lines.append("  stream against resident: {:5.2f}x".format(res[1][0] / res[0][0]))
+                res = [res[0]] + res[2:]
             best = min(res[1:], key=lambda r: r[0])
             spread = max(res[0][2] - res[0][1], best[2] - best[1])
             verdict = "LOSES" if res[0][0] > best[0] + spread else "wins" if res[0][0] + spread < best[0] else "level"
@@ -122,17 +135,33 @@ def main():
 
         img = torch.randn(B, 800, 1333, 3, device=dev, generator=g).bfloat16()
 
-        def forward(block_backend, layer_backend):
+        committed = N.SEP_AUTO_EXCLUDED
+
+        def forward(block_backend, layer_backend, excluded=None):
             set_layers(net, layer_backend)
             net.block_backend = block_backend
-            return net(img)
+            N.SEP_AUTO_EXCLUDED = committed if excluded is None else frozenset(excluded)
+            try:
+                return net(img)
+            finally:
+                N.SEP_AUTO_EXCLUDED = committed
 
+        # 'auto' three ways: with the committed constant, with what this run found losing, and with every stream form
+        # left to the layers, which is the forward before sepblock_stream.hip (blocks 1 to 6 fused, 7 to 13 as layers)
+        before = [(ci, co, s) for _, (_, _, ci, co, s) in block_forms(800, 1333) if N.sepblock_form(ci, co) == "stream"]
         res = rounds([lambda: forward("native", "native"), lambda: forward("auto", "native"),
+                      lambda: forward("auto", "native", losers), lambda: forward("auto", "native", before),
                       lambda: forward("torch", "native"), lambda: forward("torch", "torch")], calls=3)
-        forward("auto", "native")
+        taken = []
+        for excluded in (None, losers, before):
+            forward("auto", "native", excluded)
+            taken.append(" ".join(net.block_taken))
         lines.append("MobileNet(1.0).eval() forward, batch {} of 800 x 1333 ({} rounds x 3 calls); under block_backend = "
-                     "'auto' the blocks run as: {}".format(B, ROUNDS, " ".join(net.block_taken)))
-        names = ("block_backend 'native' over native layers", "block_backend 'auto' over native layers", "native layers",
+                     "'auto' the blocks run as: {}".format(B, ROUNDS, taken[0]))
+        lines.append("  with this run's losing forms excluded: {}".format(taken[1]))
+        lines.append("  with the stream forms excluded:        {}".format(taken[2]))
+        names = ("block_backend 'native' over native layers", "block_backend 'auto' over native layers",
+                 "'auto', this run's losing forms excluded", "'auto', stream forms excluded (as before)", "native layers",
                  "torch layers")
         for name, (med, lo, hi) in zip(names, res):
             lines.append("  {:<42} {:9.1f} us ({:9.1f} .. {:9.1f})".format(name, med, lo, hi))
